@@ -1,9 +1,20 @@
 #!/usr/bin/env python3
 """Benchmark: Whisper Large-V3 Q4_0 real-time factor on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and no more: load the model,
+put the inputs in HBM, warm up, time the K steps, write the last step's
+outputs if `--dump-outputs DIR` is given (tokens.npy / n_tokens.npy, float32;
+the inputs depend only on the arguments, so two builds can be compared output
+for output), and print one JSON line: metric, value, unit, higher_is_better,
+dtype, ms_per_step (wall ms of one timed step) and what the timed steps
+themselves recorded (phase times, per-category kernel events).  `--full` adds
+everything that takes runs of its own after the timed steps: value_sequential,
+the PCIe-inclusive value, the kernel probes with the roofline entries, and
+the CPU baseline -- all described below.
 
 Both forms run N ranks: without a torch.distributed.run environment
 (WORLD_SIZE unset) and N > 1, this process starts the N rank processes
@@ -407,6 +418,108 @@ def dry_run(args, rank: int, world: int) -> None:
         dist.destroy_process_group()
 
 
+def dump_outputs(out_dir: str, toks: list[list[int]], max_tokens: int, rank: int, world: int) -> None:
+    """--dump-outputs: what the timed path returned for its last step -- the
+    token ids of that batch's clips (special tokens excluded), as float32
+    [clips, max_tokens] padded with -1, and the tokens per clip [clips].  One
+    pair of files per rank (suffix _rank<r> in a multi-rank run).  Token ids
+    are < 2^24, exact in float32."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arr = np.full((len(toks), max_tokens), -1.0, np.float32)
+    for i, t in enumerate(toks):
+        arr[i, : len(t)] = t
+    sfx = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(out_dir, f"tokens{sfx}.npy"), arr)
+    np.save(os.path.join(out_dir, f"n_tokens{sfx}.npy"), np.array([len(t) for t in toks], np.float32))
+
+
+def rooflines(args, cfg: dict, prec: int, B: int, group_rows: int, prof: dict, probe: dict, phase: dict,
+              steps_run: float) -> dict:
+    """--full: the roofline entries of the result line, from the Q4 GEMM HIP
+    events of the timed steps (prof), the kernel probes run after them (probe)
+    and the committed profiles of this workload."""
+    import wq4
+
+    workload = {"variant": args.variant, "weights": args.weights, "precision": args.precision, "clips": B}
+    q4 = prof["q4_gemm"]
+    # north-star kernel: the encoder's Q4 MFMA GEMMs, timed live per launch;
+    # the kernel that ran them at this row count (tile or ring kernel)
+    enc_rows = B * cfg["n_audio_ctx"]
+    enc_kernel = wq4.gemm_kernel_name(cfg["n_audio_state"], cfg["n_audio_state"], enc_rows)
+    q4_tf = q4["gflop"] / (q4["ms"] * 1e-3) * 1e-3 if q4["ms"] > 0 else 0.0
+    roof_q4 = {"bound": "mfma", "achieved": round(q4_tf, 2), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
+               "frac": round(q4_tf / PEAK_MFMA_TFLOPS, 4),
+               "traffic": pmc_traffic(enc_kernel, workload),
+               "kernel": f"{enc_kernel} (encoder Q4 GEMMs, M = {enc_rows})",
+               "launches": q4["launches"], "avg_us": round(q4["ms"] / max(1, q4["launches"]) * 1e3, 2),
+               "gpu_ms_per_step": round(q4["ms"] / args.steps, 2)}
+    # decode phase: cross-attention (HBM stream of the encoder-output planes), probed after the timed steps
+    xa = probe["cross_attention"]
+    xa_gbs = xa["bytes"] / (xa["us"] * 1e-6) * 1e-9
+    groups = -(-B // group_rows)
+    kv = xa["kv_cache"]  # few clips: the GEMV over the cached cross K / V (one launch)
+    ig = None if kv else in_graph_xattn(group_rows, cfg["n_text_head"], cfg["n_text_state"], workload)
+    xa_kernel = ("cross-attention over the cached cross K / V: cross_attn_kv_kernel" if kv else
+                 "cross-attention over the encoder output: xattn_q + xattn_main + xattn_out")
+    roof_xa = {"bound": "hbm", "achieved": round(xa_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+               "frac": round(xa_gbs / PEAK_HBM_GBS, 4),
+               "traffic": None if kv else pmc_traffic_xattn_probe(group_rows, cfg["n_text_head"],
+                                                                  cfg["n_text_state"], workload),
+               "kernel": f"{xa_kernel} "
+                         f"(decode step, Tq = 1, {group_rows} clips per launch = one of {groups} decode groups)",
+               "avg_us": round(xa["us"], 2), "bytes_per_launch": xa["bytes"],
+               "in_graph_avg_us": None if ig is None else round(ig, 2),
+               "in_graph_frac": None if ig is None else round(xa["bytes"] / (ig * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4),
+               # summed over both decode groups' launches (they overlap in wall time)
+               "gpu_ms_per_step": round(xa["us"] * 1e-3 * cfg["n_text_layer"] * steps_run * groups, 2)}
+    dq = probe["decode_fc1"]
+    roof_dq = {"bound": "hbm", "achieved": round(dq["bytes"] / (dq["us"] * 1e-6) * 1e-9, 1),
+               "peak": PEAK_HBM_GBS, "unit": "GB/s",
+               "frac": round(dq["bytes"] / (dq["us"] * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4), "traffic": None,
+               "kernel": f"q4_gemm_decode_kernel (decode-step fc1, split-K, {group_rows} rows)",
+               "avg_us": round(dq["us"], 2),
+               "tflops": round(dq["flops"] / (dq["us"] * 1e-6) * 1e-12, 2)}
+    # the decode step as a whole: algorithmic bytes per step / measured wall time per step
+    ns = 2 if prec == wq4.PREC_F16X2 else 1
+    kv_avg = 4.0 + (steps_run + 1) / 2.0  # prompt (4) + the steps so far, averaged over the loop
+    sb = decode_step_bytes(cfg, B, groups, kv, args.weights, ns, kv_avg)
+    step_ms = phase["decode_ms"] / max(1.0, steps_run)
+    ds_gbs = sb["total"] / (step_ms * 1e-3) * 1e-9
+    roof_ds = {"bound": "hbm", "achieved": round(ds_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+               "frac": round(ds_gbs / PEAK_HBM_GBS, 4), "traffic": None,
+               "kernel": f"one greedy decode step (all {groups} decode groups, {B} clips), wall time",
+               "ms_per_step": round(step_ms, 4), "bytes_per_step": {k: int(v) for k, v in sb.items()},
+               "kv_avg": kv_avg, "floor_ms_per_step": round(sb["total"] / (PEAK_HBM_GBS * 1e9) * 1e3, 4)}
+    # wall-time share (like for like with the serial encoder GEMMs): the
+    # groups' launches overlap, so summed GPU time is scaled by the
+    # union / sum of the same family's intervals in the committed trace
+    ov = decode_overlap(workload)
+    fam = None if ov is None else ov["families"].get("cross_attention")
+    if fam is not None:
+        roof_xa["wall_ms_per_step"] = round(roof_xa["gpu_ms_per_step"] * fam["union_over_sum"], 2)
+        roof_xa["wall_ms_source"] = "profiles/decode_overlap.json (union / sum of the family's in-graph intervals)"
+    else:  # no committed trace of this workload: the groups' launches taken as perfectly overlapped
+        roof_xa["wall_ms_per_step"] = round(roof_xa["gpu_ms_per_step"] / groups, 2)
+        roof_xa["wall_ms_source"] = f"estimate: summed GPU ms / {groups} decode groups (no committed trace)"
+    main = None if ov is None else ov["families"].get("xattn_main_kernel")
+    if main and not kv:
+        mb = group_rows * cfg["n_audio_ctx"] * cfg["n_text_state"] * 2.0 * ns  # planes per launch
+        cg = mb * main["launches"] / (main["union_us"] * 1e-6) * 1e-9
+        roof_xa["concurrent_main"] = {
+            "source": "profiles/decode_overlap.json", "launches": main["launches"],
+            "sum_us": main["sum_us"], "union_us": main["union_us"], "achieved_gbs": round(cg, 1),
+            "frac": round(cg / PEAK_HBM_GBS, 4),
+            "note": "encoder-plane bytes of every xattn_main launch of both groups over the union of their "
+                    "intervals (wall time with at least one running)"}
+    xa_wall = roof_xa["wall_ms_per_step"]
+    roof_q4["wall_ms_per_step"] = roof_q4["gpu_ms_per_step"]  # one stream: GPU time is wall time
+    dominant = roof_xa if xa_wall > roof_q4["wall_ms_per_step"] else roof_q4
+    return {"roofline": dominant, "roofline_q4_gemm": roof_q4, "roofline_cross_attention": roof_xa,
+            "roofline_decode_gemm": roof_dq, "roofline_decode_step": roof_ds}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -427,19 +540,26 @@ def main() -> None:
     ap.add_argument("--sequential", action="store_true",
                     help="one wa_transcribe per step (no encoder / decode pipelining across steps)")
     ap.add_argument("--seq-steps", type=int, default=3,
-                    help="pipelined runs: batches then timed one wa_transcribe each, for value_sequential "
+                    help="--full, pipelined runs: batches then timed one wa_transcribe each, for value_sequential "
                          "(0 = skip)")
     ap.add_argument("--cpu-rows", type=int, default=160,
-                    help="rows the single-core CPU baseline times at M = 1500 (scaled to 1500)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: rows the single-core CPU baseline times at M = 1500 (scaled to 1500)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline figure: "
+                         "value_sequential, the PCIe-inclusive value, the kernel probes and rooflines, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's token ids as DIR/tokens.npy and DIR/n_tokens.npy (float32)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / max-over-ranks only, no GPU work (CPU test of --gpus N)")
     args = ap.parse_args()
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     rank = int(os.environ.get("RANK", "0"))
@@ -530,6 +650,7 @@ def main() -> None:
     ntok = []
     timings = []
     pipe = None
+    toks = None  # the last timed step's token ids (--dump-outputs)
     t0 = time.perf_counter()
     if pipelined:
         for toks in model.transcribe_batches(timed_in, lang, args.max_tokens, eot_stop=eot):
@@ -547,11 +668,15 @@ def main() -> None:
     elapsed = time.perf_counter() - t0
     model.profile_enable(False)
     prof = model.profile_read(reset=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, toks, args.max_tokens, rank, world)
+    # Everything below the timed steps that takes GPU or CPU runs of its own
+    # is --full only; a plain run goes straight to its result line.
     # The same batches one wa_transcribe each (the reference's loop: one
     # transcribe, encoder then decode, per call) -- reported beside the
     # pipelined `value`, never as it.
     seq_elapsed = None
-    n_seq = min(args.seq_steps, args.steps) if pipelined else 0
+    n_seq = min(args.seq_steps, args.steps) if pipelined and args.full else 0
     if n_seq > 0:
         torch.cuda.synchronize()
         if dist:
@@ -565,99 +690,27 @@ def main() -> None:
         seq_elapsed = max_over_ranks(time.perf_counter() - t2, dist, "cpu")
     # PCIe-inclusive figure (never `value`): one batch's inputs from pinned host
     # memory to HBM, timed after the timed steps and added per step
-    host_in = inputs[0].cpu().pin_memory()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(3):
-        inputs[0].copy_(host_in, non_blocking=True)
-    torch.cuda.synchronize()
-    h2d_s = (time.perf_counter() - t1) / 3
-    elapsed_pcie = max_over_ranks(elapsed + args.steps * h2d_s, dist, "cpu")
+    h2d_s = elapsed_pcie = None
+    if args.full:
+        host_in = inputs[0].cpu().pin_memory()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(3):
+            inputs[0].copy_(host_in, non_blocking=True)
+        torch.cuda.synchronize()
+        h2d_s = (time.perf_counter() - t1) / 3
+        elapsed_pcie = max_over_ranks(elapsed + args.steps * h2d_s, dist, "cpu")
     elapsed = max_over_ranks(elapsed, dist, "cpu")
     clips = world * B * args.steps
     value = job_rtf(world, B, args.steps, elapsed)
 
     group_rows = whisper_amd.decode_group_rows(B)
-    probe = model.probe_kernels(group_rows, iters=20) if rank == 0 else None
+    probe = model.probe_kernels(group_rows, iters=20) if args.full and rank == 0 else None
     if rank == 0:
-        workload = {"variant": args.variant, "weights": args.weights, "precision": args.precision, "clips": B}
-        q4 = prof["q4_gemm"]
         mean_tok = float(np.mean(ntok)) if ntok else 0.0
         steps_run = float(np.mean([t["steps"] for t in timings])) if timings else 0.0
-        # north-star kernel: the encoder's Q4 MFMA GEMMs, timed live per launch;
-        # the kernel that ran them at this row count (tile or ring kernel)
-        enc_rows = B * cfg["n_audio_ctx"]
-        enc_kernel = wq4.gemm_kernel_name(cfg["n_audio_state"], cfg["n_audio_state"], enc_rows)
-        q4_tf = q4["gflop"] / (q4["ms"] * 1e-3) * 1e-3 if q4["ms"] > 0 else 0.0
-        roof_q4 = {"bound": "mfma", "achieved": round(q4_tf, 2), "peak": PEAK_MFMA_TFLOPS, "unit": "TFLOP/s",
-                   "frac": round(q4_tf / PEAK_MFMA_TFLOPS, 4),
-                   "traffic": pmc_traffic(enc_kernel, workload),
-                   "kernel": f"{enc_kernel} (encoder Q4 GEMMs, M = {enc_rows})",
-                   "launches": q4["launches"], "avg_us": round(q4["ms"] / max(1, q4["launches"]) * 1e3, 2),
-                   "gpu_ms_per_step": round(q4["ms"] / args.steps, 2)}
-        # decode phase: cross-attention (HBM stream of the encoder-output planes), probed after the timed steps
-        xa = probe["cross_attention"]
-        xa_gbs = xa["bytes"] / (xa["us"] * 1e-6) * 1e-9
-        groups = -(-B // group_rows)
-        kv = xa["kv_cache"]  # few clips: the GEMV over the cached cross K / V (one launch)
-        ig = None if kv else in_graph_xattn(group_rows, cfg["n_text_head"], cfg["n_text_state"], workload)
-        xa_kernel = ("cross-attention over the cached cross K / V: cross_attn_kv_kernel" if kv else
-                     "cross-attention over the encoder output: xattn_q + xattn_main + xattn_out")
-        roof_xa = {"bound": "hbm", "achieved": round(xa_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                   "frac": round(xa_gbs / PEAK_HBM_GBS, 4),
-                   "traffic": None if kv else pmc_traffic_xattn_probe(group_rows, cfg["n_text_head"],
-                                                                      cfg["n_text_state"], workload),
-                   "kernel": f"{xa_kernel} "
-                             f"(decode step, Tq = 1, {group_rows} clips per launch = one of {groups} decode groups)",
-                   "avg_us": round(xa["us"], 2), "bytes_per_launch": xa["bytes"],
-                   "in_graph_avg_us": None if ig is None else round(ig, 2),
-                   "in_graph_frac": None if ig is None else round(xa["bytes"] / (ig * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4),
-                   # summed over both decode groups' launches (they overlap in wall time)
-                   "gpu_ms_per_step": round(xa["us"] * 1e-3 * cfg["n_text_layer"] * steps_run * groups, 2)}
-        dq = probe["decode_fc1"]
-        roof_dq = {"bound": "hbm", "achieved": round(dq["bytes"] / (dq["us"] * 1e-6) * 1e-9, 1),
-                   "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                   "frac": round(dq["bytes"] / (dq["us"] * 1e-6) * 1e-9 / PEAK_HBM_GBS, 4), "traffic": None,
-                   "kernel": f"q4_gemm_decode_kernel (decode-step fc1, split-K, {group_rows} rows)",
-                   "avg_us": round(dq["us"], 2),
-                   "tflops": round(dq["flops"] / (dq["us"] * 1e-6) * 1e-12, 2)}
-        # the decode step as a whole: algorithmic bytes per step / measured wall time per step
         phase = {k: float(np.mean([t[k] for t in timings])) for k in ("encoder_ms", "cross_kv_ms", "prompt_ms",
                                                                          "decode_ms")}
-        ns = 2 if prec == wq4.PREC_F16X2 else 1
-        kv_avg = 4.0 + (steps_run + 1) / 2.0  # prompt (4) + the steps so far, averaged over the loop
-        sb = decode_step_bytes(cfg, B, groups, kv, args.weights, ns, kv_avg)
-        step_ms = phase["decode_ms"] / max(1.0, steps_run)
-        ds_gbs = sb["total"] / (step_ms * 1e-3) * 1e-9
-        roof_ds = {"bound": "hbm", "achieved": round(ds_gbs, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                   "frac": round(ds_gbs / PEAK_HBM_GBS, 4), "traffic": None,
-                   "kernel": f"one greedy decode step (all {groups} decode groups, {B} clips), wall time",
-                   "ms_per_step": round(step_ms, 4), "bytes_per_step": {k: int(v) for k, v in sb.items()},
-                   "kv_avg": kv_avg, "floor_ms_per_step": round(sb["total"] / (PEAK_HBM_GBS * 1e9) * 1e3, 4)}
-        # wall-time share (like for like with the serial encoder GEMMs): the
-        # groups' launches overlap, so summed GPU time is scaled by the
-        # union / sum of the same family's intervals in the committed trace
-        ov = decode_overlap(workload)
-        fam = None if ov is None else ov["families"].get("cross_attention")
-        if fam is not None:
-            roof_xa["wall_ms_per_step"] = round(roof_xa["gpu_ms_per_step"] * fam["union_over_sum"], 2)
-            roof_xa["wall_ms_source"] = "profiles/decode_overlap.json (union / sum of the family's in-graph intervals)"
-        else:  # no committed trace of this workload: the groups' launches taken as perfectly overlapped
-            roof_xa["wall_ms_per_step"] = round(roof_xa["gpu_ms_per_step"] / groups, 2)
-            roof_xa["wall_ms_source"] = f"estimate: summed GPU ms / {groups} decode groups (no committed trace)"
-        main = None if ov is None else ov["families"].get("xattn_main_kernel")
-        if main and not kv:
-            mb = group_rows * cfg["n_audio_ctx"] * cfg["n_text_state"] * 2.0 * ns  # planes per launch
-            cg = mb * main["launches"] / (main["union_us"] * 1e-6) * 1e-9
-            roof_xa["concurrent_main"] = {
-                "source": "profiles/decode_overlap.json", "launches": main["launches"],
-                "sum_us": main["sum_us"], "union_us": main["union_us"], "achieved_gbs": round(cg, 1),
-                "frac": round(cg / PEAK_HBM_GBS, 4),
-                "note": "encoder-plane bytes of every xattn_main launch of both groups over the union of their "
-                        "intervals (wall time with at least one running)"}
-        xa_wall = roof_xa["wall_ms_per_step"]
-        roof_q4["wall_ms_per_step"] = roof_q4["gpu_ms_per_step"]  # one stream: GPU time is wall time
-        dominant = roof_xa if xa_wall > roof_q4["wall_ms_per_step"] else roof_q4
         line = {
             "metric": METRIC, "value": round(value, 3), "unit": "audio-s/wall-s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
@@ -670,11 +723,11 @@ def main() -> None:
                        "model": f"whisper-{args.variant.replace('_', '-')}-{args.weights} (synthetic weights)",
                        "global_batch": clips // args.steps, "seq_len": cfg["n_audio_ctx"],
                        "parallelism": f"replicas{world} (independent clips, no collectives)"},
-            "roofline": dominant,
-            "roofline_q4_gemm": roof_q4,
-            "roofline_cross_attention": roof_xa,
-            "roofline_decode_gemm": roof_dq,
-            "roofline_decode_step": roof_ds,
+            "full": args.full,
+        }
+        if args.full:
+            line.update(rooflines(args, cfg, prec, B, group_rows, prof, probe, phase, steps_run))
+        line.update({
             "kernels": {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
                             "tflops": round(v["gflop"] / (v["ms"] * 1e-3) * 1e-3, 2) if v["ms"] else None,
                             "gbs": round(v["gb"] / (v["ms"] * 1e-3), 1) if v["ms"] else None}
@@ -688,20 +741,23 @@ def main() -> None:
                 "= encoder time per batch not hidden by a decode; the Q4 GEMM events cover the full-width "
                 "launches only")),
             "input": "16 kHz audio in HBM (GPU log-mel timed)" if args.audio else "log-mel in HBM",
-            "input_h2d_ms_per_step": round(h2d_s * 1e3, 3),
-            "value_pcie_inclusive": round(job_rtf(world, B, args.steps, elapsed_pcie), 3),
-            "value_sequential": None if seq_elapsed is None else round(job_rtf(world, B, n_seq, seq_elapsed), 3),
-            "ms_per_step_sequential": None if seq_elapsed is None else round(seq_elapsed / n_seq * 1e3, 3),
             "value_note": ("value: pipelined serving throughput (one wa_transcribe_batches call; the next batch's "
-                           "encoder beside the current decode); value_sequential: the same batches one "
+                           "encoder beside the current decode); with --full, value_sequential: the same batches one "
                            "wa_transcribe each, the reference's transcribe-per-call loop (whisper.rs:51-128) -- "
                            "the like-for-like figure for the reference (BASELINE.md section 3); both with the "
                            "mels resident in HBM, value_pcie_inclusive adds their H2D copy")
             if pipelined else "one wa_transcribe per step (the reference's loop), mels resident in HBM",
             "log_mel_ms": round(float(np.mean(mel_ms)), 3) if mel_ms else None,
             "model_load_s": round(t_load, 2),
-        }
-        line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(model.config, args.cpu_rows, mean_tok)
+        })
+        if args.full:
+            line.update({
+                "input_h2d_ms_per_step": round(h2d_s * 1e3, 3),
+                "value_pcie_inclusive": round(job_rtf(world, B, args.steps, elapsed_pcie), 3),
+                "value_sequential": None if seq_elapsed is None else round(job_rtf(world, B, n_seq, seq_elapsed), 3),
+                "ms_per_step_sequential": None if seq_elapsed is None else round(seq_elapsed / n_seq * 1e3, 3),
+                "cpu_baseline": None if args.no_cpu_baseline else cpu_baseline(model.config, args.cpu_rows, mean_tok),
+            })
         s = json.dumps(line)
         print(s, flush=True)
         if args.json_out:

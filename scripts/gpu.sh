@@ -5,7 +5,7 @@
 # cite are copied into profiles/ by hand.
 #
 #   suite           GPU parity suite (-m gpu, verbose prints) + smoke()
-#   bench           default bench line                        -> bench.json
+#   bench           default bench line, with --full           -> bench.json
 #   configs         BASELINE configs 2, 3, 5 (32 / 1 clip) and f16 precision
 #   trace           kernel trace of the bench's decode (BENCH_ARGS; 24 tokens):
 #                   tools/timeline.py, per-grid durations, in-graph xattn summary
@@ -31,7 +31,7 @@ ROOT=$(pwd)
 
 bench_line() {  # name, bench args...
   local n=$1; shift
-  timeout -k 10 600 python bench.py "$@" --json-out "$O/$n.json" > "$O/$n.log" 2>&1 || { tail -20 "$O/$n.log"; return 1; }
+  timeout -k 10 600 python bench.py --full "$@" --json-out "$O/$n.json" > "$O/$n.log" 2>&1 || { tail -20 "$O/$n.log"; return 1; }
   python3 -c "import json; d=json.load(open('$O/$n.json')); print('$n', d['value'], d['unit'], d['phase_ms'], 'xattn us', d['roofline_cross_attention']['avg_us'], 'q4 TF', d['roofline_q4_gemm']['achieved'])"
 }
 
@@ -91,7 +91,7 @@ task_pmc() {
 
 task_stats() {
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/stats" -o run --output-format csv -- python3 bench.py --steps 1 --warmup 1 \
-    --no-cpu-baseline $BENCH_ARGS --json-out "$O/bench_under_rocprof.json" > "$O/stats.log" 2>&1 || return 1
+    --full --no-cpu-baseline $BENCH_ARGS --json-out "$O/bench_under_rocprof.json" > "$O/stats.log" 2>&1 || return 1
   cp "$(ls "$O"/stats/*/run_kernel_stats.csv "$O"/stats/run_kernel_stats.csv 2>/dev/null | head -1)" "$O/kernel_stats.csv"
   # the Q4 GEMM launches per queue: full width (what roofline_q4_gemm times) vs the CU-masked encoder stream
   python3 scripts/kernel_by_queue.py "$(trace_csv "$O/stats")" "q4_gemm_wide|q4_gemm_prefill|q4_gemm_enc" \

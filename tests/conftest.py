@@ -39,6 +39,22 @@ _ensure_built()
 
 @pytest.fixture(scope="session")
 def golden():
+    """The reference quantizer's vectors (tests/golden/make_golden.py):
+    q4_golden.npz plus one q4_golden_<case>.npz per large random case, read as
+    one mapping with an .npz file's `files` list."""
+    import glob
+
     import numpy as np
 
-    return np.load(os.path.join(REPO, "tests", "golden", "q4_golden.npz"))
+    class Golden(dict):
+        @property
+        def files(self):
+            return list(self)
+
+    out = Golden()
+    for path in sorted(glob.glob(os.path.join(REPO, "tests", "golden", "q4_golden*.npz"))):
+        with np.load(path) as f:
+            for k in f.files:
+                assert k not in out, f"{k} stored twice ({path})"
+                out[k] = f[k]
+    return out

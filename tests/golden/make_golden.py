@@ -35,6 +35,9 @@ def load_reference_quantizer():
     return mod
 
 
+LARGE_CASES = ("normal_0.02", "normal_0.05", "normal_1.0", "uniform_pm1")  # 32 * 4096 values each
+
+
 def cases() -> dict[str, np.ndarray]:
     rng = np.random.default_rng(20260227)
     c: dict[str, np.ndarray] = {}
@@ -97,9 +100,15 @@ def main() -> None:
     out["names/hf"] = np.array(hf)
     out["names/gguf"] = np.array([ref.hf_name_to_gguf(h) for h in hf])
     out["meta/numpy_version"] = np.array(np.__version__)
-    path = os.path.join(HERE, "q4_golden.npz")
-    np.savez_compressed(path, **out)
-    print(f"wrote {path}: {len(out)} arrays, {os.path.getsize(path)} bytes")
+    # one file per large random case keeps every fixture file under 1 MiB;
+    # tests/conftest.py's `golden` reads them back as one mapping
+    parts = {"q4_golden.npz": {k: v for k, v in out.items() if k.split("/", 1)[1] not in LARGE_CASES}}
+    for name in LARGE_CASES:
+        parts[f"q4_golden_{name}.npz"] = {k: out[k] for k in (f"in/{name}", f"q4/{name}")}
+    for fname, arrays in parts.items():
+        path = os.path.join(HERE, fname)
+        np.savez_compressed(path, **arrays)
+        print(f"wrote {path}: {len(arrays)} arrays, {os.path.getsize(path)} bytes")
 
 
 if __name__ == "__main__":

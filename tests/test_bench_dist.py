@@ -60,6 +60,24 @@ def test_job_value_is_whole_job_aggregate():
     assert bench.clip_ids(1, 2, 1, 1) == [[4, 5], [6, 7]]
 
 
+def test_dump_outputs_writes_padded_float32(tmp_path):
+    """--dump-outputs: token ids [clips, max_tokens] padded with -1 and the
+    per-clip counts, float32, one pair per rank in a multi-rank run."""
+    import numpy as np
+
+    import bench
+
+    toks = [[50364, 7, 51865], [], [1, 2]]
+    bench.dump_outputs(str(tmp_path / "one"), toks, 4, 0, 1)
+    t = np.load(tmp_path / "one" / "tokens.npy")
+    assert t.dtype == np.float32
+    assert np.array_equal(t, [[50364, 7, 51865, -1], [-1, -1, -1, -1], [1, 2, -1, -1]])
+    n = np.load(tmp_path / "one" / "n_tokens.npy")
+    assert n.dtype == np.float32 and np.array_equal(n, [3, 0, 2])
+    bench.dump_outputs(str(tmp_path / "two"), toks, 4, 1, 2)
+    assert sorted(os.listdir(tmp_path / "two")) == ["n_tokens_rank1.npy", "tokens_rank1.npy"]
+
+
 def _init_rank(rank: int, world: int, port: int, q) -> None:
     os.environ.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port), "RANK": str(rank),
                        "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank)})
