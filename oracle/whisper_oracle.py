@@ -19,7 +19,7 @@ model-level golden tokens: parity of tokens is "unpinned" with
 respect to the reference binary and pinned to this restatement.
 
 The synthetic weights are generated exactly as the product does
-(whisper-burn_amd/csrc/whisper/wa_model.cpp build_synthetic): same names,
+(whisper-burn_amd/csrc/whisper/wa_weights.cpp SynthSource, build_model): same names,
 same ranges, same generator (oracle.synth_uniform).
 """
 from __future__ import annotations

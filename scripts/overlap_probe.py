@@ -3,7 +3,8 @@ clips (encoder + two-group decode) while model B, on its own CU-masked
 stream (WA_ENC_CU_MASK=N at its creation), runs encoders back to back in a
 second thread.  Prints A's phase times alone and with B running, and B's
 encoder time alone and under A's decode.   python3 scripts/overlap_probe.py N
-(WA_ENC_CU_MASK lived in the r02 experiment build of wa_model.cpp only: the
+(WA_ENC_CU_MASK lived in the r02 experiment build of the model runtime only
+-- the masked stream is now wa_transcribe.cpp ensure_enc_stream -- and the
 mask did not restrict the encoder, DESIGN.md §4 dead ends.)"""
 import os
 import sys

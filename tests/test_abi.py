@@ -177,7 +177,7 @@ def test_every_whisper_header_function_is_exported():
 def test_decode_group_rows():
     """wa_decode_group_rows: the clips of the largest decode group (the row
     count of every captured decode-step launch and of bench.py's probe): one
-    group below 16 clips, two from 16 on (wa_model.cpp decode_groups)."""
+    group below 16 clips, two from 16 on (wa_forward.cpp decode_groups)."""
     import whisper_amd
 
     assert whisper_amd.decode_group_rows(0) == 0

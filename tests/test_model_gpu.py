@@ -174,7 +174,7 @@ def test_f16_gguf_checkpoint(torch, tmp_path):
 
 def test_two_decode_groups_match_oracle(torch, oracle_model, gpu_model):
     """16 clips take the two-stream decode path (two groups of 8, each its own
-    graph and KV cache, wa_model.cpp decode_groups); their tokens must equal
+    graph and KV cache, wa_forward.cpp decode_groups); their tokens must equal
     the single-group path's (batches of 4) and the oracle's for a sample."""
     import whisper_amd
 
@@ -213,7 +213,7 @@ def test_ragged_eot_stop_matches_oracle(torch, tmp_path, eot_scale):
     got = g.transcribe(torch.from_numpy(mel).cuda(), 50259, max_tokens=24)
     assert got == want
     # a decode group whose clips have all emitted EOT stops replaying (the
-    # host's lag-4 poll of n_done, wa_model.cpp): when every clip of one
+    # host's lag-4 poll of n_done, wa_transcribe.cpp run_decode): when every clip of one
     # group of 8 stops early, fewer than max_tokens steps run
     longest = [max(len(t) for t in want[i:i + 8]) for i in (0, 8)]
     steps = g.last_timings()["steps"]

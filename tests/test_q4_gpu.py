@@ -444,7 +444,7 @@ def test_gemm_headmajor_layout(torch, policy):
 
 @pytest.mark.parametrize("clips,mode", [(1, 1), (2, 1), (2, 5), (9, 5)])
 def test_gemm_headmajor_ring_kernel(torch, clips, mode):
-    """The few-clip cross K / V cache GEMMs (wa_model.cpp cross_kv_forward:
+    """The few-clip cross K / V cache GEMMs (wa_forward.cpp cross_kv_forward:
     M = clips x 1500 rows, head-major output) run on the encoder ring kernel
     (wq4_enc.hip; mode 5: the wide kernel, wq4_wide.hip); their bits equal
     the prefill tile kernel's row-major result permuted to [g][head][t][64]."""

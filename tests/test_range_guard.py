@@ -202,6 +202,30 @@ def test_value_overflow_recovers_oracle_tokens(tmp_path):
 
 
 @pytest.mark.gpu
+def test_value_overflow_recovers_without_cross_kv_caches(tmp_path):
+    """Range tier 3 over the cache-free cross-attention (its f32 output, which
+    the 2-clip runs above never reach: they decode over the cached K / V).
+    WA_XATTN_KV_CLIPS is read once per process, so the transcribe runs in a
+    child interpreter (tests/knob_child.py with the GGUF path)."""
+    import json
+    import subprocess
+    import sys
+
+    t32, _, _, _, _ = oracle_run("value")
+    env = dict(os.environ)
+    for k in ("WQ4_KERNEL_POLICY", "WA_LN_FOLD", "WA_DECODE_GROUPS"):
+        env.pop(k, None)
+    env["WA_XATTN_KV_CLIPS"] = "0"
+    child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "knob_child.py")
+    r = subprocess.run([sys.executable, child, _write("value", tmp_path)], env=env, capture_output=True, text=True,
+                       timeout=100)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    assert got["range_tier"] == 3
+    assert got["tokens"] == t32
+
+
+@pytest.mark.gpu
 def test_normal_model_never_flags():
     import torch
 

@@ -1,10 +1,10 @@
 """The product's environment tuning knobs, each run end to end (GPU).
 
 Every knob only re-plans work the default path already does -- the
-LayerNorm fold off (wa_model.cpp lnfold_on: WA_LN_FOLD),
-another number of decode groups (wa_model.cpp decode_groups:
+LayerNorm fold off (wa_forward.cpp lnfold_on: WA_LN_FOLD),
+another number of decode groups (wa_forward.cpp decode_groups:
 WA_DECODE_GROUPS) or the cross-attention over cached K / V for more clips
-(wa_model.cpp kv_config: WA_XATTN_KV_CLIPS, whose groups then also form
+(wa_forward.cpp kv_config: WA_XATTN_KV_CLIPS, whose groups then also form
 their qkv / query projections inside the attention launches) -- so the greedy tokens of 16 synthetic tiny_test clips
 must equal the default's, and a sample must equal the oracle's
 (oracle/whisper_oracle.py).  The knobs are read once per process, so each

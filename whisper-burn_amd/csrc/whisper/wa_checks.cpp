@@ -1,0 +1,209 @@
+// wa_checks.cpp -- C ABI entries that run one kernel on caller-supplied
+// buffers (the wa_*_check test entries) and the log-mel front-end.
+#include <map>
+#include <mutex>
+
+#include "wa_mel.hpp"
+#include "wa_model.hpp"
+
+using namespace wa;
+
+namespace {
+
+int planes(wq4_precision prec) { return prec == WQ4_PREC_F16 ? 1 : 2; }
+
+// The scaffold of the attention checks: `launch` writes R rows of width D as
+// the A-tiled GEMM operand into a zeroed buffer, returned as f32 rows.
+template <class Launch>
+wq4_status tiled_check(Dev& d, int64_t R, int D, wq4_precision prec, float* out_dev, Launch launch) {
+  const size_t tb = wq4_atiled_bytes(R, D, prec);
+  auto* tiled = d.alloc<_Float16>(tb / 2);
+  if (!tiled) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemset(tiled, 0, tb));
+  WA_HIP(launch(tiled));
+  WA_HIP(launch_untile(tiled, (int)R, D, planes(prec), out_dev, nullptr));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+wq4_status wa_xattn_check(int device, const float* q_dev, const uint8_t* wk_dev, const uint8_t* wv_dev,
+                          const float* bv_dev, int weight_type, const float* enc_dev, int n_clips, int Tq, int T,
+                          int H, wq4_precision prec, float* out_dev) {
+  if (!q_dev || !wk_dev || !wv_dev || !bv_dev || !enc_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || Tq < 1 || T < 1 || H < 1) return fail(WQ4_EINVAL, "bad sizes");
+  const int D = 64 * H, ns = planes(prec), R = n_clips * Tq;
+  const int HP = (H + 15) / 16 * 16;
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  auto* enc = d.alloc<_Float16>((size_t)n_clips * T * ns * D);
+  auto* qt = d.alloc<_Float16>((size_t)R * ns * HP * D);
+  auto* part = d.alloc<float>(xattn_part_floats(R, H, D, T));
+  if (!enc || !qt || !part) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemset(qt, 0, (size_t)R * ns * HP * D * 2));
+  WA_HIP(launch_enc_planes(enc_dev, (int64_t)n_clips * T, D, ns, enc, nullptr));
+  uint32_t* wvp = nullptr;
+  if (weight_type == 0) {
+    wvp = d.alloc<uint32_t>(wv_pack_words(H, D));
+    if (!wvp) return fail(WQ4_ENOMEM, "allocation failed");
+    WA_HIP(launch_wv_pack(wv_dev, H, D, wvp, nullptr));
+  }
+  return tiled_check(d, R, D, prec, out_dev, [&](_Float16* tiled) {
+    return launch_xattn(q_dev, wk_dev, wv_dev, wvp, bv_dev, weight_type, enc, n_clips, Tq, T, H, D, qt, part, tiled,
+                        ns, nullptr);
+  });
+}
+
+wq4_status wa_xattn_kv_check(int device, const float* q_dev, const float* k_dev, const float* v_dev, int n_clips,
+                             int Tq, int T, int H, wq4_precision prec, float* out_dev) {
+  if (!q_dev || !k_dev || !v_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || Tq < 1 || Tq > 4 || T < 1 || H < 1) return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  auto* part = d.alloc<float>(cross_attention_kv_part_floats(n_clips, H, T));
+  auto* ctr = d.alloc<int>((size_t)n_clips * H);
+  if (!part || !ctr) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemset(ctr, 0, (size_t)n_clips * H * sizeof(int)));
+  return tiled_check(d, n_clips * Tq, 64 * H, prec, out_dev, [&](_Float16* tiled) {
+    return launch_cross_attention_kv(q_dev, k_dev, v_dev, n_clips, Tq, T, H, part, ctr, tiled, planes(prec), nullptr);
+  });
+}
+
+wq4_status wa_encoder_attention_check(int device, const float* qkv_dev, int n_clips, int T, int H, wq4_precision prec,
+                                      float* out_dev) {
+  if (!qkv_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || T < 1 || H < 1) return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  return tiled_check(d, (int64_t)n_clips * T, 64 * H, prec, out_dev, [&](_Float16* tiled) {
+    return launch_encoder_attention(qkv_dev, n_clips, T, H, tiled, planes(prec), nullptr);
+  });
+}
+
+wq4_status wa_self_attention_check(int device, const float* qkv_dev, float* cache_k_dev, float* cache_v_dev,
+                                   int n_clips, int Tq, int H, int ctx, int kv_len, wq4_precision prec,
+                                   float* out_dev) {
+  if (!qkv_dev || !cache_k_dev || !cache_v_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || Tq < 1 || Tq > 4 || H < 1 || ctx < 1 || ctx > 448 || kv_len < 0 || kv_len + Tq > ctx)
+    return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  return tiled_check(d, n_clips * Tq, 64 * H, prec, out_dev, [&](_Float16* tiled) {
+    return launch_decoder_self_attention(qkv_dev, cache_k_dev, cache_v_dev, n_clips, Tq, H, ctx, nullptr, kv_len,
+                                         tiled, planes(prec), nullptr);
+  });
+}
+
+wq4_status wa_logits_argmax_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                  int step, wq4_precision prec, int32_t* tok_dev, float* logits_dev) {
+  if (!hid_dev || !emb_dev || !tok_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > 32 || V < 1 || !emb_tiled_supported(D)) return fail(WQ4_EINVAL, "bad sizes");
+  const int ns = planes(prec);
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  const int64_t erows = emb_tiled_rows(V);
+  const int ng = logits_argmax_groups(V);
+  auto* emb2 = d.alloc<_Float16>((size_t)erows * ns * D);
+  auto* st = d.alloc<DecodeState>(1);
+  auto* pval = d.alloc<float>((size_t)32 * ng);
+  auto* pidx = d.alloc<int>((size_t)32 * ng);
+  auto* ctr = d.alloc<int>(1);
+  const size_t tb = wq4_atiled_bytes(n_clips, D, prec);
+  auto* ht = d.alloc<_Float16>(tb / 2);
+  int* ids = nullptr;
+  if (logits_dev) ids = d.alloc<int>((size_t)n_clips * 2 * V);
+  if (!emb2 || !st || !pval || !pidx || !ctr || !ht || (logits_dev && !ids))
+    return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(launch_emb_tiled(emb_dev, V, D, ns, emb2, nullptr));
+  WA_WQ4(wq4_tile_activations(hid_dev, n_clips, D, D, prec, ht, tb, nullptr));
+  // A trace writes slot state->step + 1 of [clip][2][V] (every id listed at
+  // slot 1): the state's step is then 0 and the EOT suppression of `step`
+  // (step + 1 < 3, whisper.rs:120-122) is passed through min_tokens instead.
+  const DecodeState s0{0, 0, logits_dev ? 0 : step, 0};
+  const int min_tokens = !logits_dev ? kMinTokens : (step + 1 < kMinTokens ? 1 << 30 : 0);
+  WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  WA_HIP(hipMemset(ctr, 0, sizeof(int)));
+  float* tr = nullptr;
+  if (logits_dev) {
+    std::vector<int> h((size_t)n_clips * 2 * V, 0);
+    for (int b = 0; b < n_clips; ++b)
+      for (int v = 0; v < V; ++v) h[((size_t)b * 2 + 1) * V + v] = v;
+    WA_HIP(hipMemcpy(ids, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    tr = d.alloc<float>((size_t)n_clips * 2 * V);
+    if (!tr) return fail(WQ4_ENOMEM, "allocation failed");
+  }
+  WA_HIP(launch_logits_argmax(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, ctr, tok_dev, ids, tr, 2, V,
+                              nullptr, nullptr));
+  if (logits_dev)
+    for (int b = 0; b < n_clips; ++b)
+      WA_HIP(hipMemcpy(logits_dev + (size_t)b * V, tr + ((size_t)b * 2 + 1) * V, (size_t)V * 4,
+                       hipMemcpyDeviceToDevice));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- log-mel --
+// Per-device constants (window, filterbank, twiddles; per n_mels) and the
+// per-workgroup-max scratch, allocated on first use outside stream capture.
+namespace {
+struct MelDevice {
+  std::map<int, uint8_t*> consts;
+  float* part = nullptr;
+  int part_clips = 0;
+};
+std::mutex g_mel_mu;
+std::map<int, MelDevice> g_mel;
+}  // namespace
+
+extern "C" {
+
+wq4_status wa_log_mel(int device, const float* audio_dev, int n_clips, int64_t n_samples, int64_t ld_audio,
+                      int n_mels, float* mel_dev, void* stream) {
+  if (!mel_dev || (!audio_dev && n_samples > 0)) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1) return fail(WQ4_EINVAL, "n_clips must be >= 1");
+  if (n_samples < 0 || ld_audio < n_samples) return fail(WQ4_EINVAL, "need 0 <= n_samples <= ld_audio");
+  if (n_mels < 1 || n_mels > kMelMaxMels) return fail(WQ4_EINVAL, "n_mels must be in [1, 256]");
+  WA_HIP(hipSetDevice(device));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> lk(g_mel_mu);
+  MelDevice& md = g_mel[device];
+  uint8_t*& c = md.consts[n_mels];
+  if (!c || md.part_clips < n_clips) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    WA_HIP(hipStreamIsCapturing(st, &cs));
+    if (cs != hipStreamCaptureStatusNone)
+      return fail(WQ4_EINVAL, "wa_log_mel: run once outside stream capture first (allocates constants)");
+  }
+  if (!c) {
+    const MelBank bank = make_mel_bank(n_mels);
+    std::vector<uint8_t> host(mel_const_bytes(n_mels));
+    mel_pack_consts(bank, host.data());
+    WA_HIP(hipMalloc(reinterpret_cast<void**>(&c), host.size()));
+    WA_HIP(hipMemcpy(c, host.data(), host.size(), hipMemcpyHostToDevice));
+  }
+  if (md.part_clips < n_clips) {
+    WA_HIP(hipDeviceSynchronize());
+    if (md.part) WA_HIP(hipFree(md.part));
+    md.part = nullptr;
+    md.part_clips = 0;
+    WA_HIP(hipMalloc(reinterpret_cast<void**>(&md.part), (size_t)n_clips * kMelWgPerClip * sizeof(float)));
+    md.part_clips = n_clips;
+  }
+  WA_HIP(launch_log_mel(audio_dev, n_clips, n_samples, ld_audio, n_mels, c, md.part, mel_dev, st));
+  return WQ4_OK;
+}
+
+wq4_status wa_mel_filterbank(int n_mels, float* filters_out, float* window_out) {
+  if (n_mels < 1 || n_mels > kMelMaxMels) return fail(WQ4_EINVAL, "n_mels must be in [1, 256]");
+  const MelBank bank = make_mel_bank(n_mels);
+  if (filters_out) std::memcpy(filters_out, bank.filters.data(), bank.filters.size() * sizeof(float));
+  if (window_out) std::memcpy(window_out, bank.window.data(), bank.window.size() * sizeof(float));
+  return WQ4_OK;
+}
+
+}  // extern "C"

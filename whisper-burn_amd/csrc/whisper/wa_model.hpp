@@ -1,0 +1,288 @@
+// wa_model.hpp -- internal: the Whisper model runtime's state (struct
+// wa_model) and what its translation units (wa_weights, wa_forward,
+// wa_transcribe, wa_api, wa_checks .cpp) need from one another.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../../include/whisper_amd.h"
+#include "../../../include/wq4.h"
+#include "wa_gguf.hpp"
+#include "wa_kernels.hpp"
+
+namespace wa {
+
+// records the calling thread's error string (wa_last_error) and returns s
+wq4_status fail(wq4_status s, const std::string& m);
+
+#define WA_HIP(expr)                                                                                \
+  do {                                                                                              \
+    hipError_t e_ = (expr);                                                                         \
+    if (e_ != hipSuccess) return wa::fail(WQ4_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+#define WA_WQ4(expr)                                                                    \
+  do {                                                                                  \
+    wq4_status s_ = (expr);                                                             \
+    if (s_ != WQ4_OK) return wa::fail(s_, std::string(#expr) + ": " + wq4_last_error()); \
+  } while (0)
+// a call that has already recorded its error
+#define WA_TRY(expr)             \
+  do {                           \
+    wq4_status s_ = (expr);      \
+    if (s_ != WQ4_OK) return s_; \
+  } while (0)
+
+constexpr int kMaxTokens = 224;  // whisper.rs:20
+constexpr int kMinTokens = 3;    // whisper.rs:97
+
+struct Config {  // WhisperConfig, src/model/config.rs:5-30
+  int n_mels, n_audio_ctx, n_audio_state, n_audio_head, n_audio_layer;
+  int n_text_ctx, n_text_state, n_text_head, n_text_layer, n_vocab, n_lang;
+  int transcribe_token() const { return 50260 + n_lang; }      // config.rs:66-69
+  int no_timestamps_token() const { return transcribe_token() + 4; }  // config.rs:72-74
+};
+
+struct Dev {
+  std::vector<void*> ptrs;
+  ~Dev() {
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  template <class T>
+  T* alloc(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, n * sizeof(T) + 256) != hipSuccess) return nullptr;
+    ptrs.push_back(p);
+    return static_cast<T*>(p);
+  }
+  // frees one pointer alloc() returned (null: no-op)
+  void release(void* p) {
+    if (!p) return;
+    for (void*& q : ptrs)
+      if (q == p) {
+        (void)hipFree(q);
+        q = ptrs.back();
+        ptrs.pop_back();
+        return;
+      }
+  }
+};
+
+struct EncLayer {
+  float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *qkv_b, *out_b, *fc1_b, *fc2_b;
+  wq4_tensor *qkv = nullptr, *out = nullptr, *fc1 = nullptr, *fc2 = nullptr;
+};
+struct DecLayer {
+  float *ln1_w, *ln1_b, *ln2_w, *ln2_b, *ln3_w, *ln3_b;
+  float *qkv_b, *out_b, *cq_b, *cv_b, *cout_b, *fc1_b, *fc2_b;
+  wq4_tensor *qkv = nullptr, *out = nullptr, *cq = nullptr, *cout = nullptr, *fc1 = nullptr, *fc2 = nullptr;
+  // LayerNorm fold (wq4_gemm_tiled_lnfold) of the GEMMs that read a
+  // LayerNorm: W gamma and W beta + bias of qkv (attn_ln), cq
+  // (cross_attn_ln), fc1 (mlp_ln)
+  float *qkv_wg = nullptr, *qkv_b2 = nullptr, *cq_wg = nullptr, *cq_b2 = nullptr, *fc1_wg = nullptr,
+        *fc1_b2 = nullptr;
+  // cross-attention key / value weights in raw GGUF form (Q4_0 blocks or
+  // f16), read by the K/V-cache-free cross-attention (wa_xattn.hip)
+  uint8_t *ck_raw = nullptr, *cv_raw = nullptr;
+  uint32_t* cv_p = nullptr;  // Q4_0: cv_raw in the projection's lane order (wa::launch_wv_pack)
+  float *cache_k, *cache_v;
+  // few-clip decode groups (wa_model::kv_clips): the reference's per-layer
+  // cross K / V caches, head-major [clip][head][T][64] f32, written by the
+  // head-major GEMMs of ck / cv over the encoder output (cross_kv_forward)
+  wq4_tensor *ck = nullptr, *cv = nullptr;
+  float *xk = nullptr, *xv = nullptr;
+};
+
+// One decode group: a contiguous range of clips [b0, b0 + nb) decoded on its
+// own stream with its own activations, DecodeState and step graph.  The
+// decode step is a chain of ~350 small dependent kernels (latency-bound);
+// groups on separate streams overlap one another's launch gaps and let the
+// HBM-bound cross-attention of one group run beside the latency-bound GEMMs
+// of another.  Per-clip results do not depend on the grouping (every
+// kernel's per-row arithmetic is independent of the batch).
+constexpr int kMaxGroups = 4;
+struct DecGroup {
+  hipStream_t st = nullptr;
+  int b0 = 0, nb = 0;
+  float *xd, *qkvd, *qd, *hid, *logits;
+  _Float16 *atd_dec, *atf_dec;
+  int *prompt_tok, *next_tok, *tokens, *ntok, *done;
+  _Float16* xqt;    // cross-attention Wk^T q operands [rows][ns][16*ceil(H/16)][D]
+  float* xattn_part;  // cross-attention split partials (Z, max, sum)
+  float* xkv_part;    // cross-attention over cached K / V: split partials
+  int* xkv_ctr;       //   and the per-(clip, head) arrival counters
+  _Float16* atd_ln;   // LayerNorm fold: A-tiled x * gamma of the next LayerNorm
+  float* ln_stats;    //                 its per (row, 32-column tile) mean / M2
+  _Float16* hid_t;    // fused logits + argmax: the final LN, A-tiled (m-tile 0)
+  float* lg_val;      //                        per-workgroup candidates [32][groups]
+  int *lg_idx, *lg_ctr;
+  DecodeState* state;
+  void* ffn_ws = nullptr;  // range tier 2: wq4_ffn_forward_ws workspace (4 * nb rows)
+  size_t ffn_ws_bytes = 0;
+  int* host_ndone = nullptr;  // pinned ring
+  hipGraphExec_t graph = nullptr;
+  int64_t graph_key = -1;  // (b0, nb, eot mode, trace) the graph was captured for
+};
+
+}  // namespace wa
+
+struct wa_model {
+  int device = 0;
+  wa::Config cfg{};
+  wq4_precision prec = WQ4_PREC_F16X2;
+  int ns = 2;
+  int bmax = 1;
+  wa::Dev dev;
+  size_t bytes = 0;
+  // globals
+  float *conv1_wt, *conv1_b, *conv2_wt, *conv2_b, *enc_pos, *lnp_w, *lnp_b;
+  float *tok_emb, *dec_pos, *dln_w, *dln_b;
+  _Float16* tok_emb2 = nullptr;  // tied embedding as fragment-tiled f16 pairs (wa::launch_emb_tiled)
+  std::vector<wa::EncLayer> enc;
+  std::vector<wa::DecLayer> dec;
+  // encoder activations
+  float *h1, *x, *qkv;
+  _Float16 *at_d, *at_f;
+  // encoder output as f16 planes [clip][T][ns][D], the cross-attention's
+  // only per-clip state (no per-layer K/V caches)
+  _Float16* enc_planes = nullptr;
+  const float* enc_f32 = nullptr;  // ln_post output of the last encoder pass
+  // decode groups: the clips of a transcribe split over up to kMaxGroups
+  // independent streams, each replaying its own step graph (see DecGroup)
+  std::vector<wa::DecGroup> groups;
+  int wtype = 0;     // linear weights: 0 Q4_0, 1 f16 (BASELINE config 5)
+  int kv_batch = 0;  // clips of the last encoder pass (enc_planes valid for [0, kv_batch))
+  // Cross K / V caches (capacity kv_clips clips) for transcribes of at most
+  // kv_small clips -- their decode steps are launch-latency chains: one GEMV
+  // launch over the caches replaces the cache-free cross-attention's four,
+  // wa_kernels.hip.  kv_n: clips [0, kv_n) of the last encoder pass have
+  // caches; a decode group entirely inside them reads the caches.
+  int kv_clips = 0, kv_small = 0;
+  int kv_n = 0;
+  bool kv_alloc_ok = false;  // every layer's xk / xv allocated (cross_kv_forward)
+  bool group_kv(const wa::DecGroup& g) const { return g.nb > 0 && g.b0 + g.nb <= kv_n; }
+  hipStream_t own_stream = nullptr;  // encoder / encoder planes (graph capture needs a non-null stream)
+  // pipelined transcribes (wa_transcribe_batches): the CU-masked stream of
+  // the encoder part that runs beside a decode, its CU count, the encoder
+  // layers that part covers (adapted per batch) and the last call's stats
+  hipStream_t enc_stream = nullptr;
+  int enc_cus = 0;
+  int overlap_k = -1;
+  int overlap_b = 0, overlap_eot = -1;  // the batch shape overlap_k was adapted to
+  float pipe[4] = {0, 0, 0, 0};
+  // Activation-range guard.  Every internal producer writes MFMA operands as
+  // f16 pairs of x * 2^4 (wq4_device.hpp split_act), finite for |x| < 4094;
+  // beyond that the f16 half overflows and the clip's logits become inf /
+  // NaN.  The pick kernels set *range_flag on any non-finite logit.  After a
+  // flagged transcribe the model retries it one range tier up (wa_transcribe;
+  // sticky for the model); flagged at the last tier -> WQ4_ERANGE, never NaN
+  // tokens.
+  int* range_flag = nullptr;
+  int range_tier = 0;
+  // tier 1: the LayerNorm fold is off (the fold feeds the RAW residual stream
+  // x * gamma to the MFMAs, where the LayerNorm path feeds LayerNorm(x),
+  // bounded by sqrt(D) |gamma| + |beta|).
+  bool fold_allowed() const { return range_tier < 1; }
+  // tier 2: the encoder and decoder FFNs run as Q4FFN::forward at the ABI
+  // (wq4_ffn_forward_ws: LayerNorm output in f32, fc1 + GELU to f32, each
+  // GEMM operand scaled by a power of two picked per call from its max |x|),
+  // so fc1 / GELU outputs of any f32-finite size reach fc2 finite.
+  // Workspaces allocated when the tier is entered: ffn_ws for the encoder's
+  // B * T rows, g.ffn_ws per decode group.
+  bool abi_ffn() const { return range_tier >= 2; }
+  // tier 3: every attention output (encoder self-attention, decoder self- and
+  // cross-attention) is written as f32 rows instead of the f16-pair operand,
+  // and the output projections run as Q4Linear::forward at the ABI
+  // (wq4_linear_forward_ws: per-call operand scale).  Scratch: m->h1 (free
+  // during the encoder layers) / g.hid, with the layer's own A-tiled buffer
+  // as the ABI workspace.
+  bool f32_attn() const { return range_tier >= 3; }
+  void* ffn_ws = nullptr;
+  size_t ffn_ws_bytes = 0;
+  float timings[5] = {0, 0, 0, 0, 0};
+  // decode-step logit trace (wa_transcribe_trace; null otherwise): device
+  // [clip][trace_s1][trace_k] ids and their logits
+  const int* trace_ids = nullptr;
+  float* trace_out = nullptr;
+  int trace_s1 = 0, trace_k = 0;
+  // live kernel timing (wa_profile_*)
+  struct Pending {
+    hipEvent_t a, b;
+    int cat;
+    double gflop, gb;
+  };
+  bool profile = false;
+  std::vector<Pending> pending;
+  double prof[WA_PROF_CATEGORIES][4] = {};
+
+  void resolve_profile() {
+    for (auto& p : pending) {
+      float ms = 0.0f;
+      if (hipEventSynchronize(p.b) == hipSuccess && hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+        prof[p.cat][0] += 1;
+        prof[p.cat][1] += ms;
+        prof[p.cat][2] += p.gflop;
+        prof[p.cat][3] += p.gb;
+      }
+      (void)hipEventDestroy(p.a);
+      (void)hipEventDestroy(p.b);
+    }
+    pending.clear();
+  }
+
+  ~wa_model() {
+    resolve_profile();
+    for (auto& g : groups) {
+      if (g.graph) (void)hipGraphExecDestroy(g.graph);
+      if (g.st) (void)hipStreamDestroy(g.st);
+      if (g.host_ndone) (void)hipHostFree(g.host_ndone);
+    }
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    if (enc_stream) (void)hipStreamDestroy(enc_stream);
+    for (auto& l : enc)
+      for (wq4_tensor* t : {l.qkv, l.out, l.fc1, l.fc2}) wq4_tensor_destroy(t);
+    for (auto& l : dec)
+      for (wq4_tensor* t : {l.qkv, l.out, l.cq, l.cout, l.fc1, l.fc2, l.ck, l.cv}) wq4_tensor_destroy(t);
+  }
+};
+
+namespace wa {
+
+// ---- wa_weights.cpp
+Config preset(int variant);
+// Where the weights come from: the synthetic generator (no checkpoint is
+// available offline) or a GGUF file (loader.rs).  Names are the GGUF names.
+struct Source {
+  virtual ~Source() = default;
+  // n f32 values of `name`; false (no error) when an optional tensor is absent
+  virtual bool f32(const std::string& name, int64_t n, float lo, float hi, bool optional, std::vector<float>& out) = 0;
+  // the [rows, k] linear weight `name` in raw GGUF form written at dst: Q4_0
+  // blocks (wtype 0) or f16 halves (wtype 1, config 5)
+  virtual bool linear(const std::string& name, int rows, int k, int wtype, uint8_t* dst) = 0;
+  std::string err;
+};
+std::unique_ptr<Source> synth_source(uint64_t seed);
+std::unique_ptr<Source> gguf_source(const GgufFile& f);
+wq4_status build_model(wa_model* m, Source& src);
+wq4_status build_ln_fold(wa_model* m);
+
+// ---- wa_forward.cpp
+void kv_config(wa_model* m, int max_batch);
+wq4_status alloc_activations(wa_model* m);
+wq4_status ensure_ffn_ws(wa_model* m);
+int decode_groups(int B);
+wq4_status encoder_front(wa_model* m, const float* mel, int B, hipStream_t st);
+wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);
+wq4_status encoder_post(wa_model* m, int B, hipStream_t st, float* enc_out_f32);
+wq4_status encoder_forward(wa_model* m, const float* mel, int B, hipStream_t st, float* enc_out_f32);
+wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches);
+wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, const DecodeState* state, int pos0,
+                           int kv0, hipStream_t st);
+wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st);
+wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop);
+
+}  // namespace wa

@@ -1,0 +1,428 @@
+// wa_transcribe.cpp -- the transcribe drivers (WhisperModel::transcribe,
+// src/model/whisper.rs:51-128): one batch, software-pipelined batches, and
+// the range-tier retries around them.
+#include "wa_model.hpp"
+
+using namespace wa;
+
+namespace {
+
+// Pipelined transcribes (transcribe_pipelined): CUs of the encoder stream
+// that runs beside a decode, the encoder layers it covers in the first
+// overlapped batch, and the share of the last decode's length its part is
+// sized to afterwards (WA_ENC_CUS / WA_ENC_OVERLAP / WA_ENC_FILL override).
+// Fill measured at 32 clips (scripts/r05ad.sh): RTF 959 at 0.92, 966 at 0.98
+// / 1.0 / 1.02, 948 at 1.04 (the masked part then outlasts the decode);
+// 0.98 keeps ~30 ms of slack.
+constexpr int kEncOverlapCUs = 32;
+constexpr int kEncOverlapLayers0 = 16;
+constexpr double kEncOverlapFill = 0.98;
+
+// HIP events destroyed with the set.
+struct EventSet {
+  std::vector<hipEvent_t> e;
+  EventSet() = default;
+  EventSet(const EventSet&) = delete;
+  EventSet& operator=(const EventSet&) = delete;
+  ~EventSet() {
+    for (hipEvent_t x : e) (void)hipEventDestroy(x);
+  }
+  hipError_t make(hipEvent_t* out, bool timing = true) {
+    hipError_t r = hipEventCreateWithFlags(out, timing ? hipEventDefault : hipEventDisableTiming);
+    if (r == hipSuccess) e.push_back(*out);
+    return r;
+  }
+};
+
+// Prompt + greedy loop (whisper.rs:60-125) of every decode group of a batch
+// of B clips, each group's stream first waiting on `ready` (the encoder
+// planes of the batch).  Records gprompt[i] after group i's prompt and
+// gdone[i] after its last step; the host blocks only for the lagged EOT
+// polls (eot_stop).
+wq4_status run_decode(wa_model* m, int B, int lang_token, int max_tokens, int eot_stop, hipEvent_t ready,
+                      const hipEvent_t* gprompt, const hipEvent_t* gdone, int* steps_out) {
+  const int G = decode_groups(B);
+  for (int i = 0; i < G; ++i) {
+    DecGroup& g = m->groups[i];
+    g.b0 = (int)((int64_t)B * i / G);
+    g.nb = (int)((int64_t)B * (i + 1) / G) - g.b0;
+    WA_HIP(hipStreamWaitEvent(g.st, ready, 0));
+    WA_TRY(prompt_group(m, g, lang_token, g.st));
+    WA_HIP(hipEventRecord(gprompt[i], g.st));
+    WA_TRY(ensure_graph(m, g, eot_stop));
+  }
+  // greedy loop (whisper.rs:104-125): each step replays every live group's
+  // graph; a group stops once all its clips emitted EOT (polled with a lag)
+  EventSet ev;
+  hipEvent_t ring[kMaxGroups][8];
+  if (eot_stop)
+    for (int i = 0; i < G; ++i)
+      for (auto& e : ring[i]) WA_HIP(ev.make(&e, false));
+  int steps = 0;
+  const int lag = 4;
+  bool live[kMaxGroups] = {};
+  int nlive = G;
+  for (int i = 0; i < G; ++i) live[i] = true;
+  for (int step = 0; step < max_tokens && nlive > 0; ++step) {
+    for (int i = 0; i < G; ++i) {
+      if (!live[i]) continue;
+      DecGroup& g = m->groups[i];
+      WA_HIP(hipGraphLaunch(g.graph, g.st));
+      if (eot_stop) {
+        const int slot = step % 8;
+        WA_HIP(hipMemcpyAsync(&g.host_ndone[slot], &g.state->n_done, sizeof(int), hipMemcpyDeviceToHost, g.st));
+        WA_HIP(hipEventRecord(ring[i][slot], g.st));
+      }
+    }
+    ++steps;
+    if (eot_stop && step >= lag) {
+      const int old = (step - lag) % 8;
+      for (int i = 0; i < G; ++i) {
+        if (!live[i]) continue;
+        WA_HIP(hipEventSynchronize(ring[i][old]));
+        if (m->groups[i].host_ndone[old] >= m->groups[i].nb) {  // every clip had emitted EOT by then
+          live[i] = false;
+          --nlive;
+        }
+      }
+    }
+  }
+  // the loop's bookkeeping for tokens chosen by the last step happens at the
+  // top of a step that the reference never runs: nothing to add.
+  for (int i = 0; i < G; ++i) WA_HIP(hipEventRecord(gdone[i], m->groups[i].st));
+  *steps_out = steps;
+  return WQ4_OK;
+}
+
+// `st` waits for every group of the batch, then copies the groups' tokens /
+// counts (kMaxTokens per clip) and the range flag to (pinned) host memory.
+wq4_status collect_batch(wa_model* m, int B, const hipEvent_t* gdone, hipStream_t st, int32_t* tok, int32_t* nt,
+                         int* flag) {
+  const int G = decode_groups(B);
+  for (int i = 0; i < G; ++i) WA_HIP(hipStreamWaitEvent(st, gdone[i], 0));
+  for (int i = 0; i < G; ++i) {
+    const DecGroup& g = m->groups[i];
+    WA_HIP(hipMemcpyAsync(tok + (size_t)g.b0 * kMaxTokens, g.tokens, (size_t)g.nb * kMaxTokens * 4,
+                          hipMemcpyDeviceToHost, st));
+    WA_HIP(hipMemcpyAsync(nt + g.b0, g.ntok, (size_t)g.nb * 4, hipMemcpyDeviceToHost, st));
+  }
+  WA_HIP(hipMemcpyAsync(flag, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  return WQ4_OK;
+}
+
+void copy_tokens(const int32_t* tok, const int32_t* nt, int B, int max_tokens, int32_t* tokens_out,
+                 int32_t* n_tokens_out) {
+  for (int b = 0; b < B; ++b) {
+    n_tokens_out[b] = std::min(nt[b], max_tokens);
+    std::memcpy(tokens_out + (size_t)b * max_tokens, tok + (size_t)b * kMaxTokens, (size_t)max_tokens * 4);
+  }
+}
+
+// One transcribe (whisper.rs:51-128 for a batch of clips); *overflow = the
+// range flag of this run (see wa_model::range_flag).
+wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                           int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, bool* overflow) {
+  // all work on the model's own stream, ordered after the caller's stream
+  hipStream_t st = m->own_stream;
+  const int B = n_clips;
+  const int G = decode_groups(B);
+  EventSet ev;
+  hipEvent_t e_in, e_enc, e_kv, e_ready, e_end, gprompt[kMaxGroups], gdone[kMaxGroups];
+  for (hipEvent_t* e : {&e_in, &e_enc, &e_kv, &e_ready, &e_end}) WA_HIP(ev.make(e));
+  for (int i = 0; i < G; ++i) {
+    WA_HIP(ev.make(&gprompt[i]));
+    WA_HIP(ev.make(&gdone[i]));
+  }
+  WA_HIP(hipEventRecord(e_in, static_cast<hipStream_t>(stream)));
+  WA_HIP(hipStreamWaitEvent(st, e_in, 0));
+  WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
+
+  WA_HIP(hipEventRecord(e_enc, st));
+  WA_TRY(encoder_forward(m, mel_dev, B, st, nullptr));
+  WA_HIP(hipEventRecord(e_kv, st));
+  WA_TRY(cross_kv_forward(m, B, st, true));
+  WA_HIP(hipEventRecord(e_ready, st));
+  // decode groups: contiguous clip ranges on their own streams, started
+  // after the encoder-planes pass, joined back into `st` at the end
+  int steps = 0;
+  WA_TRY(run_decode(m, B, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, &steps));
+  std::vector<int32_t> tok((size_t)B * kMaxTokens), nt(B);
+  int flag = 0;
+  WA_TRY(collect_batch(m, B, gdone, st, tok.data(), nt.data(), &flag));
+  WA_HIP(hipEventRecord(e_end, st));
+  WA_HIP(hipStreamSynchronize(st));
+  *overflow = flag != 0;
+  copy_tokens(tok.data(), nt.data(), B, max_tokens, tokens_out, n_tokens_out);
+  // phases: encoder, encoder planes (the cross-attention state), prompt (slowest group), decode loop
+  float t_enc = 0.0f, t_kv = 0.0f, tp = 0.0f, tall = 0.0f;
+  WA_HIP(hipEventElapsedTime(&t_enc, e_enc, e_kv));
+  WA_HIP(hipEventElapsedTime(&t_kv, e_kv, e_ready));
+  for (int i = 0; i < G; ++i) {
+    float t = 0.0f;
+    WA_HIP(hipEventElapsedTime(&t, e_ready, gprompt[i]));
+    tp = std::max(tp, t);
+  }
+  WA_HIP(hipEventElapsedTime(&tall, e_ready, e_end));
+  m->timings[0] = t_enc;
+  m->timings[1] = t_kv;
+  m->timings[2] = tp;
+  m->timings[3] = tall - tp;
+  m->timings[4] = (float)steps;
+  return WQ4_OK;
+}
+
+// The CU-masked stream of the pipelined transcribe's overlapped encoder
+// part: bits 0 .. n-1 of the mask, which the driver spreads over the XCDs
+// (bit i -> XCD i mod 8), n / 8 CUs of each; created on first use.
+wq4_status ensure_enc_stream(wa_model* m) {
+  if (m->enc_stream) return WQ4_OK;
+  hipDeviceProp_t prop;
+  WA_HIP(hipGetDeviceProperties(&prop, m->device));
+  const int total = prop.multiProcessorCount;
+  int n = kEncOverlapCUs;
+  if (const char* e = getenv("WA_ENC_CUS")) n = atoi(e);
+  n = std::max(8, std::min(total, n));
+  std::vector<uint32_t> mask((total + 31) / 32, 0u);
+  for (int i = 0; i < n; ++i) mask[i / 32] |= 1u << (i % 32);
+  WA_HIP(hipExtStreamCreateWithCUMask(&m->enc_stream, (uint32_t)mask.size(), mask.data()));
+  m->enc_cus = n;
+  return WQ4_OK;
+}
+
+// wa_transcribe over n_batches batches of n_clips clips, software-pipelined:
+// while batch i decodes (its groups' streams), the conv stem and the first
+// k encoder layers of batch i + 1 run on the CU-masked stream (a few CUs of
+// every XCD; the decode keeps the rest), and once batch i's decode is done
+// the remaining layers, ln_post and the encoder planes of batch i + 1 run
+// at full width on the model stream.  The encoder buffers are free during a
+// decode (it reads only the planes, rewritten after the decode it serves),
+// so nothing is double-buffered.  k adapts per batch to the last decode's
+// length over the masked stream's measured time per layer.  Every kernel
+// computes what it computes in wa_transcribe: the same tokens.  flags[i] =
+// batch i's range flag (the caller re-runs flagged batches).
+wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B, int lang_token, int max_tokens,
+                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags) {
+  WA_TRY(ensure_enc_stream(m));
+  hipStream_t st = m->own_stream, es = m->enc_stream;
+  const int L = (int)m->enc.size(), G = decode_groups(B);
+  const size_t mel_stride = (size_t)B * m->cfg.n_mels * 2 * m->cfg.n_audio_ctx;
+  // pinned result staging: per batch the groups' tokens, counts and range flag
+  int32_t* host = nullptr;
+  const size_t per = (size_t)B * kMaxTokens + B + 1;
+  WA_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), (size_t)NB * per * 4, 0));
+  struct HostGuard {  // an early error return may leave copies into `p` queued: drain this model's streams first
+    wa_model* m;
+    int32_t* p;
+    bool done = false;  // success: the model stream was synchronised after the last copy
+    ~HostGuard() {
+      if (!done) {
+        (void)hipStreamSynchronize(m->own_stream);
+        if (m->enc_stream) (void)hipStreamSynchronize(m->enc_stream);
+        for (DecGroup& g : m->groups)
+          if (g.st) (void)hipStreamSynchronize(g.st);
+      }
+      (void)hipHostFree(p);
+    }
+  } hg{m, host};
+  EventSet ev;
+  struct Batch {
+    hipEvent_t ready, mstart, mend, pstart, gprompt[kMaxGroups], gdone[kMaxGroups];
+    int k = 0, steps = 0;
+  };
+  std::vector<Batch> bt(NB);
+  for (Batch& b : bt) {
+    for (hipEvent_t* e : {&b.ready, &b.mstart, &b.mend, &b.pstart}) WA_HIP(ev.make(e));
+    for (int i = 0; i < G; ++i) {
+      WA_HIP(ev.make(&b.gprompt[i]));
+      WA_HIP(ev.make(&b.gdone[i]));
+    }
+  }
+  hipEvent_t e_in, e_enc0;
+  WA_HIP(ev.make(&e_in));
+  WA_HIP(ev.make(&e_enc0));
+  WA_HIP(hipEventRecord(e_in, static_cast<hipStream_t>(stream)));
+  WA_HIP(hipStreamWaitEvent(st, e_in, 0));
+  // batch 0: the whole encoder at full width
+  WA_HIP(hipEventRecord(e_enc0, st));
+  WA_TRY(encoder_forward(m, mel_dev, B, st, nullptr));
+  WA_TRY(cross_kv_forward(m, B, st, true));
+  WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
+  WA_HIP(hipEventRecord(bt[0].ready, st));
+  // the adapted depth belongs to a batch shape: a call with another clip
+  // count or EOT mode starts again from the default
+  if (m->overlap_k < 0 || m->overlap_b != B || m->overlap_eot != eot_stop) m->overlap_k = std::min(L, kEncOverlapLayers0);
+  m->overlap_b = B;
+  m->overlap_eot = eot_stop;
+  double t_exposed = 0.0, t_masked = 0.0, t_decode = 0.0, t_prompt = 0.0, k_sum = 0.0;
+  int32_t steps_all = 0;
+  for (int i = 0; i < NB; ++i) {
+    Batch& b = bt[i];
+    if (i >= 1) {
+      // batch i - 1 is decoded (and batch i's masked part done) before batch
+      // i's decode is enqueued: the GPU meanwhile runs batch i's remaining
+      // layers; adapt k to the finished decode
+      Batch& p = bt[i - 1];
+      for (int g = 0; g < G; ++g) WA_HIP(hipEventSynchronize(p.gdone[g]));
+      WA_HIP(hipEventSynchronize(p.mend));
+      float td = 0.0f, tm = 0.0f;
+      for (int g = 0; g < G; ++g) {
+        float t = 0.0f;
+        WA_HIP(hipEventElapsedTime(&t, p.ready, p.gdone[g]));
+        td = std::max(td, t);
+      }
+      WA_HIP(hipEventElapsedTime(&tm, p.mstart, p.mend));
+      if (!getenv("WA_ENC_OVERLAP")) {
+        const double per_layer = tm / (double)(p.k + 1);  // the conv stem counts as one layer
+        double fill = kEncOverlapFill;
+        if (const char* e = getenv("WA_ENC_FILL")) fill = atof(e);  // A/B only
+        m->overlap_k = std::max(0, std::min(L, (int)(fill * td / per_layer) - 1));
+      }
+    }
+    if (const char* e = getenv("WA_ENC_OVERLAP")) m->overlap_k = std::max(0, std::min(L, atoi(e)));
+    if (i + 1 < NB) {  // the masked part of batch i + 1, beside batch i's decode
+      b.k = m->overlap_k;
+      WA_HIP(hipStreamWaitEvent(es, b.ready, 0));
+      WA_HIP(hipEventRecord(b.mstart, es));
+      WA_TRY(encoder_front(m, mel_dev + (i + 1) * mel_stride, B, es));
+      WA_TRY(encoder_layers(m, B, 0, b.k, es));
+      WA_HIP(hipEventRecord(b.mend, es));
+    }
+    WA_TRY(run_decode(m, B, lang_token, max_tokens, eot_stop, b.ready, b.gprompt, b.gdone, &b.steps));
+    int32_t* hb = host + (size_t)i * per;
+    WA_TRY(collect_batch(m, B, b.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B));
+    if (i + 1 < NB) {  // the rest of batch i + 1's encoder at full width
+      WA_HIP(hipStreamWaitEvent(st, b.mend, 0));
+      WA_HIP(hipEventRecord(b.pstart, st));
+      WA_TRY(encoder_layers(m, B, b.k, L, st));
+      WA_TRY(encoder_post(m, B, st, nullptr));
+      WA_TRY(cross_kv_forward(m, B, st, true));
+      WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
+      WA_HIP(hipEventRecord(bt[i + 1].ready, st));
+    }
+  }
+  WA_HIP(hipStreamSynchronize(st));
+  hg.done = true;
+  for (int i = 0; i < NB; ++i) {
+    const int32_t* hb = host + (size_t)i * per;
+    copy_tokens(hb, hb + (size_t)B * kMaxTokens, B, max_tokens, tokens_out + (size_t)i * B * max_tokens,
+                n_tokens_out + (size_t)i * B);
+    flags[i] = hb[(size_t)B * kMaxTokens + B];
+    // per-batch phases (averaged below)
+    Batch& b = bt[i];
+    float t = 0.0f, tp = 0.0f, td = 0.0f;
+    if (i == 0) {
+      WA_HIP(hipEventElapsedTime(&t, e_enc0, b.ready));
+    } else {
+      WA_HIP(hipEventElapsedTime(&t, bt[i - 1].pstart, b.ready));
+      float tm = 0.0f;
+      WA_HIP(hipEventElapsedTime(&tm, bt[i - 1].mstart, bt[i - 1].mend));
+      t_masked += tm;
+      k_sum += bt[i - 1].k;
+    }
+    t_exposed += t;
+    for (int g = 0; g < G; ++g) {
+      float a = 0.0f, d = 0.0f;
+      WA_HIP(hipEventElapsedTime(&a, b.ready, b.gprompt[g]));
+      WA_HIP(hipEventElapsedTime(&d, b.ready, b.gdone[g]));
+      tp = std::max(tp, a);
+      td = std::max(td, d);
+    }
+    t_prompt += tp;
+    t_decode += td - tp;
+    steps_all += b.steps;
+  }
+  m->timings[0] = (float)(t_exposed / NB);
+  m->timings[1] = 0.0f;
+  m->timings[2] = (float)(t_prompt / NB);
+  m->timings[3] = (float)(t_decode / NB);
+  m->timings[4] = (float)steps_all / NB;
+  m->pipe[0] = (float)NB;
+  m->pipe[1] = NB > 1 ? (float)(k_sum / (NB - 1)) : 0.0f;
+  m->pipe[2] = NB > 1 ? (float)(t_masked / (NB - 1)) : 0.0f;
+  m->pipe[3] = (float)m->enc_cus;
+  return WQ4_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                         int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  WA_HIP(hipSetDevice(m->device));
+  // A flagged run is retried one range tier up (wa_model::range_tier), sticky
+  // for the model: its activations evidently exceed the range below.
+  //   0 -> 1  the LayerNorm fold feeds the raw residual stream to the MFMAs
+  //   1 -> 2  the FFN hidden layer (fc1 + GELU) feeds fc2 unnormalised
+  //   2 -> 3  an attention output feeds its output projection unnormalised
+  //           (tier 3 needs tier 2's workspaces, already allocated)
+  for (;;) {
+    bool overflow = false;
+    WA_TRY(transcribe_once(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
+                           &overflow));
+    if (!overflow) return WQ4_OK;
+    if (m->range_tier == 3)
+      return fail(WQ4_ERANGE,
+                  "activation overflow: an MFMA operand left the f16-pair range (|x| >= 4094 after every range tier: "
+                  "LayerNorm path, per-call FFN and attention-projection operand scales) and the logits are not finite");
+    if (m->range_tier == 1) WA_TRY(ensure_ffn_ws(m));  // entering tier 2
+    ++m->range_tier;
+  }
+}
+
+wq4_status wa_transcribe_batches(wa_model* m, const float* mel_dev, int n_batches, int n_clips, int lang_token,
+                                 int max_tokens, int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out,
+                                 void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
+  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  WA_HIP(hipSetDevice(m->device));
+  std::vector<int> flags(n_batches, 0);
+  WA_TRY(transcribe_pipelined(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
+                              n_tokens_out, stream, flags.data()));
+  const size_t mel_stride = (size_t)n_clips * m->cfg.n_mels * 2 * m->cfg.n_audio_ctx;
+  // the pipeline decoded every batch at the tier the model had on entry
+  const int tier0 = m->range_tier;
+  for (int i = 0; i < n_batches; ++i) {
+    // a flagged batch goes through wa_transcribe's range tiers on its own;
+    // once that raised the (sticky) tier, the later batches are re-run at it
+    // too -- one wa_transcribe per batch would have decoded them there
+    if (!flags[i] && m->range_tier == tier0) continue;
+    WA_TRY(wa_transcribe(m, mel_dev + i * mel_stride, n_clips, lang_token, max_tokens, eot_stop,
+                         tokens_out + (size_t)i * n_clips * max_tokens, n_tokens_out + (size_t)i * n_clips, stream));
+  }
+  return WQ4_OK;
+}
+
+wq4_status wa_last_pipeline_stats(const wa_model* m, float* out) {
+  if (!m || !out) return fail(WQ4_EINVAL, "null argument");
+  std::memcpy(out, m->pipe, sizeof(m->pipe));
+  return WQ4_OK;
+}
+
+wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                               int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const int32_t* trace_ids_dev,
+                               int trace_k, float* trace_out_dev, void* stream) {
+  if (!m || !trace_ids_dev || !trace_out_dev || trace_k < 1) return fail(WQ4_EINVAL, "bad trace arguments");
+  m->trace_ids = trace_ids_dev;
+  m->trace_out = trace_out_dev;
+  m->trace_s1 = max_tokens + 1;
+  m->trace_k = trace_k;
+  const wq4_status s = wa_transcribe(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
+                                     n_tokens_out, stream);
+  m->trace_ids = nullptr;
+  m->trace_out = nullptr;
+  m->trace_s1 = m->trace_k = 0;
+  for (DecGroup& g : m->groups) {  // the trace graphs bake in the caller's buffers: never replay them again
+    if (g.graph) (void)hipGraphExecDestroy(g.graph);
+    g.graph = nullptr;
+    g.graph_key = -1;
+  }
+  return s;
+}
+
+}  // extern "C"

@@ -107,7 +107,7 @@ def _lin(k: int) -> float:
 
 def synthetic_specs(variant: str) -> Iterator[tuple[str, tuple, float, float]]:
     """(GGUF name, PyTorch shape, lo, hi) of every tensor of the synthetic
-    model -- the table wa_model.cpp build_model() draws from."""
+    model -- the table wa_weights.cpp build_model() draws from."""
     c = CONFIGS[variant]
     D, T, M = c["n_audio_state"], c["n_audio_ctx"], c["n_mels"]
     Dt = c["n_text_state"]
