@@ -181,6 +181,7 @@ wq4_status wa_prompt_logits(wa_model* m, const int32_t* prompt_dev, int n_clips,
   WA_HIP(hipSetDevice(m->device));
   hipStream_t st = static_cast<hipStream_t>(stream);
   DecGroup& g = m->groups[0];
+  g.lane = 0;
   g.b0 = 0;
   g.nb = n_clips;
   WA_TRY(decoder_forward(m, g, prompt_dev, plen, nullptr, 0, 0, st));

@@ -285,9 +285,13 @@ wq4_status encoder_forward(wa_model* m, const float* mel, int B, hipStream_t st,
 // The caches (f32, kv_clips x n_audio_ctx x n_text_state per layer and
 // tensor: 3.9 GB for Large-V3 at 8 clips) are allocated on the first
 // transcribe of at most kv_small clips, so batches past that never hold them.
-wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches) {
+wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches, int lane) {
   const Config& c = m->cfg;
   const int64_t rows = (int64_t)B * c.n_audio_ctx;
+  if (lane == 1) {  // a paired batch's planes (more clips than the caches serve: no caches)
+    WA_HIP(launch_enc_planes(m->enc_f32, rows, c.n_audio_state, m->ns, m->enc_planes2, st));
+    return WQ4_OK;
+  }
   m->kv_batch = B;
   WA_HIP(launch_enc_planes(m->enc_f32, rows, c.n_audio_state, m->ns, m->enc_planes, st));
   m->kv_n = caches && B <= m->kv_small ? B : 0;
@@ -342,7 +346,7 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
   const int B = g.nb;
   const int64_t rows = (int64_t)B * Tq;
   const size_t self_ofs = (size_t)g.b0 * H * c.n_text_ctx * 64;
-  const _Float16* enc = m->enc_planes + (size_t)g.b0 * T * m->ns * c.n_audio_state;
+  const _Float16* enc = (g.lane ? m->enc_planes2 : m->enc_planes) + (size_t)g.b0 * T * m->ns * c.n_audio_state;
   // Decode steps fold every decoder LayerNorm into the GEMMs around it
   // (wq4_gemm_tiled_lnfold): the residual GEMM producing x also writes
   // tiled(x * gamma) and tile statistics, the GEMM reading LN(x) corrects
@@ -391,8 +395,9 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
     DecLayer& L = m->dec[li];
     // self-attention
     WA_TRY(ln_gemm(L.qkv, L.qkv_b, L.qkv_wg, L.qkv_b2, L.ln1_w, L.ln1_b, g.qkvd, nullptr, 0u));
-    WA_HIP(launch_decoder_self_attention(g.qkvd, L.cache_k + self_ofs, L.cache_v + self_ofs, B, Tq, H, c.n_text_ctx,
-                                         state, kv0, g.atd_dec, m->ns, st, a32));
+    WA_HIP(launch_decoder_self_attention(g.qkvd, (g.lane ? L.cache_k2 : L.cache_k) + self_ofs,
+                                         (g.lane ? L.cache_v2 : L.cache_v) + self_ofs, B, Tq, H, c.n_text_ctx, state,
+                                         kv0, g.atd_dec, m->ns, st, a32));
     WA_TRY(resid_gemm(L.out, L.out_b, g.atd_dec, a32, L.ln2_w));
     // cross-attention
     WA_TRY(ln_gemm(L.cq, L.cq_b, L.cq_wg, L.cq_b2, L.ln2_w, L.ln2_b, g.qd, nullptr, 0u));
@@ -492,8 +497,13 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
   // encoder-plane offsets), the EOT mode and the trace buffers, the range
   // tier; one explicit field per mixed-radix digit
   const int64_t key =
-      (((((int64_t)g.b0 * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
+      ((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
        (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier;
+  if (g.graph && g.graph_key == key) return WQ4_OK;
+  // the other layout's graph is kept: a call with an odd batch count goes
+  // from pairs to its lone last batch and the next call back again
+  std::swap(g.graph, g.graph_alt);
+  std::swap(g.graph_key, g.graph_alt_key);
   if (g.graph && g.graph_key == key) return WQ4_OK;
   if (g.graph) {
     (void)hipGraphExecDestroy(g.graph);
@@ -558,6 +568,37 @@ wq4_status ensure_ffn_ws(wa_model* m) {
   m->ffn_ws_bytes = ne;
   m->bytes += ne;
   return WQ4_OK;
+}
+
+// The second lane (wa_model::enc_planes2, DecLayer::cache_k2 / cache_v2),
+// sized like the first; false (and nothing held) when the device has no room
+// for it: the caller then decodes unpaired.
+bool ensure_pair_lane(wa_model* m) {
+  if (m->enc_planes2) return true;
+  const Config& c = m->cfg;
+  const size_t np = (size_t)m->bmax * c.n_audio_ctx * m->ns * c.n_audio_state;
+  const size_t nc = (size_t)m->bmax * c.n_text_ctx * c.n_text_state;
+  _Float16* planes = m->dev.alloc<_Float16>(np);
+  bool ok = planes != nullptr;
+  for (DecLayer& L : m->dec) {
+    if (!ok) break;
+    L.cache_k2 = m->dev.alloc<float>(nc);
+    L.cache_v2 = m->dev.alloc<float>(nc);
+    ok = L.cache_k2 && L.cache_v2;
+  }
+  if (!ok) {
+    (void)hipGetLastError();  // the failed hipMalloc is handled here
+    m->dev.release(planes);
+    for (DecLayer& L : m->dec) {
+      m->dev.release(L.cache_k2);
+      m->dev.release(L.cache_v2);
+      L.cache_k2 = L.cache_v2 = nullptr;
+    }
+    return false;
+  }
+  m->enc_planes2 = planes;
+  m->bytes += np * 2 + nc * 8 * m->dec.size();
+  return true;
 }
 
 // Number of decode groups for a batch (WA_DECODE_GROUPS overrides).

@@ -90,6 +90,8 @@ struct DecLayer {
   uint8_t *ck_raw = nullptr, *cv_raw = nullptr;
   uint32_t* cv_p = nullptr;  // Q4_0: cv_raw in the projection's lane order (wa::launch_wv_pack)
   float *cache_k, *cache_v;
+  // the second lane's self-attention caches (wa_model::ensure_pair_lane)
+  float *cache_k2 = nullptr, *cache_v2 = nullptr;
   // few-clip decode groups (wa_model::kv_clips): the reference's per-layer
   // cross K / V caches, head-major [clip][head][T][64] f32, written by the
   // head-major GEMMs of ck / cv over the encoder output (cross_kv_forward)
@@ -97,8 +99,9 @@ struct DecLayer {
   float *xk = nullptr, *xv = nullptr;
 };
 
-// One decode group: a contiguous range of clips [b0, b0 + nb) decoded on its
-// own stream with its own activations, DecodeState and step graph.  The
+// One decode group: a contiguous range of clips [b0, b0 + nb) of one lane
+// (wa_model::enc_planes / enc_planes2 and the layers' self-attention caches
+// of that lane) decoded on its own stream with its own activations, DecodeState and step graph.  The
 // decode step is a chain of ~350 small dependent kernels (latency-bound);
 // groups on separate streams overlap one another's launch gaps and let the
 // HBM-bound cross-attention of one group run beside the latency-bound GEMMs
@@ -108,6 +111,7 @@ constexpr int kMaxGroups = 4;
 struct DecGroup {
   hipStream_t st = nullptr;
   int b0 = 0, nb = 0;
+  int lane = 0;
   float *xd, *qkvd, *qd, *hid, *logits;
   _Float16 *atd_dec, *atf_dec;
   int *prompt_tok, *next_tok, *tokens, *ntok, *done;
@@ -125,7 +129,9 @@ struct DecGroup {
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (b0, nb, eot mode, trace) the graph was captured for
+  int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace) the graph was captured for
+  hipGraphExec_t graph_alt = nullptr;  // the graph `graph` replaced last (ensure_graph)
+  int64_t graph_alt_key = -1;
 };
 
 }  // namespace wa
@@ -150,6 +156,12 @@ struct wa_model {
   // encoder output as f16 planes [clip][T][ns][D], the cross-attention's
   // only per-clip state (no per-layer K/V caches)
   _Float16* enc_planes = nullptr;
+  // Second lane of the per-clip decode state (the encoder planes here, the
+  // layers' cache_k2 / cache_v2), bmax clips like the first: a paired
+  // wa_transcribe_batches decodes two batches at once, one decode group per
+  // batch, group 1 on this lane.  Allocated by the first paired call
+  // (ensure_pair_lane); all or nothing.
+  _Float16* enc_planes2 = nullptr;
   const float* enc_f32 = nullptr;  // ln_post output of the last encoder pass
   // decode groups: the clips of a transcribe split over up to kMaxGroups
   // independent streams, each replaying its own step graph (see DecGroup)
@@ -174,6 +186,7 @@ struct wa_model {
   int overlap_k = -1;
   int overlap_b = 0, overlap_eot = -1;  // the batch shape overlap_k was adapted to
   float pipe[4] = {0, 0, 0, 0};
+  int pipe_pairs = 0;  // batch pairs the last wa_transcribe_batches decoded together
   // Activation-range guard.  Every internal producer writes MFMA operands as
   // f16 pairs of x * 2^4 (wq4_device.hpp split_act), finite for |x| < 4094;
   // beyond that the f16 half overflows and the clip's logits become inf /
@@ -238,6 +251,7 @@ struct wa_model {
     resolve_profile();
     for (auto& g : groups) {
       if (g.graph) (void)hipGraphExecDestroy(g.graph);
+      if (g.graph_alt) (void)hipGraphExecDestroy(g.graph_alt);
       if (g.st) (void)hipStreamDestroy(g.st);
       if (g.host_ndone) (void)hipHostFree(g.host_ndone);
     }
@@ -279,7 +293,8 @@ wq4_status encoder_front(wa_model* m, const float* mel, int B, hipStream_t st);
 wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);
 wq4_status encoder_post(wa_model* m, int B, hipStream_t st, float* enc_out_f32);
 wq4_status encoder_forward(wa_model* m, const float* mel, int B, hipStream_t st, float* enc_out_f32);
-wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches);
+wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches, int lane = 0);
+bool ensure_pair_lane(wa_model* m);
 wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, const DecodeState* state, int pos0,
                            int kv0, hipStream_t st);
 wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st);

@@ -34,18 +34,43 @@ struct EventSet {
   }
 };
 
+// Paired decode (transcribe_pipelined): two consecutive batches of 16 .. 32
+// clips decode at once, one decode group per batch, group 1 on the model's
+// second lane.  WA_PAIR_BATCHES=0 disables (A/B runs).
+// The masked stream keeps its adapted depth beside a paired decode (it
+// reaches all L layers of the pair's first batch): at 32-row groups
+// xattn_main wants all 256 CUs and the decode slows by about what the hidden
+// layers save, but a little is left.  Large-V3 Q4_0, 32 clips, 10 steps,
+// three interleaved runs each (profiles/pair_overlap_ab.json): RTF 1146.6 /
+// 1146.2 / 1144.1 adapted (decode 721 ms, encoder exposed 106 ms per batch)
+// against 1138.0 / 1132.1 / 1134.8 with the conv stem only (673 / 161 ms).
+constexpr int kPairMinClips = 16, kPairMaxClips = 32;
+
+bool pair_enabled() {
+  static const bool enabled = [] {
+    const char* e = getenv("WA_PAIR_BATCHES");
+    return e ? atoi(e) != 0 : true;
+  }();
+  return enabled;
+}
+
+// Decode groups of one run_decode: a pair's two batches, or one batch's groups.
+int unit_groups(int B, bool pair) { return pair ? 2 : decode_groups(B); }
+
 // Prompt + greedy loop (whisper.rs:60-125) of every decode group of a batch
-// of B clips, each group's stream first waiting on `ready` (the encoder
-// planes of the batch).  Records gprompt[i] after group i's prompt and
-// gdone[i] after its last step; the host blocks only for the lagged EOT
-// polls (eot_stop).
-wq4_status run_decode(wa_model* m, int B, int lang_token, int max_tokens, int eot_stop, hipEvent_t ready,
-                      const hipEvent_t* gprompt, const hipEvent_t* gdone, int* steps_out) {
-  const int G = decode_groups(B);
+// of B clips -- or, `pair`, of two batches of B clips, group i decoding the
+// batch in lane i -- each group's stream first waiting on `ready` (the
+// encoder planes).  Records gprompt[i] after group i's prompt and gdone[i]
+// after its last step, gsteps[i] = the steps it ran; the host blocks only for
+// the lagged EOT polls (eot_stop).
+wq4_status run_decode(wa_model* m, int B, bool pair, int lang_token, int max_tokens, int eot_stop, hipEvent_t ready,
+                      const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps) {
+  const int G = unit_groups(B, pair);
   for (int i = 0; i < G; ++i) {
     DecGroup& g = m->groups[i];
-    g.b0 = (int)((int64_t)B * i / G);
-    g.nb = (int)((int64_t)B * (i + 1) / G) - g.b0;
+    g.lane = pair ? i : 0;
+    g.b0 = pair ? 0 : (int)((int64_t)B * i / G);
+    g.nb = pair ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
     WA_HIP(hipStreamWaitEvent(g.st, ready, 0));
     WA_TRY(prompt_group(m, g, lang_token, g.st));
     WA_HIP(hipEventRecord(gprompt[i], g.st));
@@ -58,23 +83,25 @@ wq4_status run_decode(wa_model* m, int B, int lang_token, int max_tokens, int eo
   if (eot_stop)
     for (int i = 0; i < G; ++i)
       for (auto& e : ring[i]) WA_HIP(ev.make(&e, false));
-  int steps = 0;
   const int lag = 4;
   bool live[kMaxGroups] = {};
   int nlive = G;
-  for (int i = 0; i < G; ++i) live[i] = true;
+  for (int i = 0; i < G; ++i) {
+    live[i] = true;
+    gsteps[i] = 0;
+  }
   for (int step = 0; step < max_tokens && nlive > 0; ++step) {
     for (int i = 0; i < G; ++i) {
       if (!live[i]) continue;
       DecGroup& g = m->groups[i];
       WA_HIP(hipGraphLaunch(g.graph, g.st));
+      ++gsteps[i];
       if (eot_stop) {
         const int slot = step % 8;
         WA_HIP(hipMemcpyAsync(&g.host_ndone[slot], &g.state->n_done, sizeof(int), hipMemcpyDeviceToHost, g.st));
         WA_HIP(hipEventRecord(ring[i][slot], g.st));
       }
     }
-    ++steps;
     if (eot_stop && step >= lag) {
       const int old = (step - lag) % 8;
       for (int i = 0; i < G; ++i) {
@@ -90,23 +117,27 @@ wq4_status run_decode(wa_model* m, int B, int lang_token, int max_tokens, int eo
   // the loop's bookkeeping for tokens chosen by the last step happens at the
   // top of a step that the reference never runs: nothing to add.
   for (int i = 0; i < G; ++i) WA_HIP(hipEventRecord(gdone[i], m->groups[i].st));
-  *steps_out = steps;
   return WQ4_OK;
 }
 
-// `st` waits for every group of the batch, then copies the groups' tokens /
-// counts (kMaxTokens per clip) and the range flag to (pinned) host memory.
-wq4_status collect_batch(wa_model* m, int B, const hipEvent_t* gdone, hipStream_t st, int32_t* tok, int32_t* nt,
-                         int* flag) {
-  const int G = decode_groups(B);
+// `st` waits for every group of the run_decode, then copies the groups'
+// tokens / counts (kMaxTokens per clip) and the range flag to (pinned) host
+// memory: tok / nt / flag of the batch in lane 0; a pair's second batch has
+// its own lane_stride int32 further on in each.
+wq4_status collect_batch(wa_model* m, int B, bool pair, const hipEvent_t* gdone, hipStream_t st, int32_t* tok,
+                         int32_t* nt, int* flag, size_t lane_stride) {
+  const int G = unit_groups(B, pair);
   for (int i = 0; i < G; ++i) WA_HIP(hipStreamWaitEvent(st, gdone[i], 0));
   for (int i = 0; i < G; ++i) {
     const DecGroup& g = m->groups[i];
-    WA_HIP(hipMemcpyAsync(tok + (size_t)g.b0 * kMaxTokens, g.tokens, (size_t)g.nb * kMaxTokens * 4,
+    const size_t ofs = g.lane * lane_stride;
+    WA_HIP(hipMemcpyAsync(tok + ofs + (size_t)g.b0 * kMaxTokens, g.tokens, (size_t)g.nb * kMaxTokens * 4,
                           hipMemcpyDeviceToHost, st));
-    WA_HIP(hipMemcpyAsync(nt + g.b0, g.ntok, (size_t)g.nb * 4, hipMemcpyDeviceToHost, st));
+    WA_HIP(hipMemcpyAsync(nt + ofs + g.b0, g.ntok, (size_t)g.nb * 4, hipMemcpyDeviceToHost, st));
   }
-  WA_HIP(hipMemcpyAsync(flag, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+  // one flag word, set by either lane: a flagged pair flags both its batches
+  for (int i = 0; i < (pair ? 2 : 1); ++i)
+    WA_HIP(hipMemcpyAsync(flag + i * lane_stride, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
   return WQ4_OK;
 }
 
@@ -144,11 +175,12 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
   WA_HIP(hipEventRecord(e_ready, st));
   // decode groups: contiguous clip ranges on their own streams, started
   // after the encoder-planes pass, joined back into `st` at the end
-  int steps = 0;
-  WA_TRY(run_decode(m, B, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, &steps));
+  int gsteps[kMaxGroups] = {};
+  WA_TRY(run_decode(m, B, false, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, gsteps));
+  const int steps = *std::max_element(gsteps, gsteps + G);  // the last group to stop
   std::vector<int32_t> tok((size_t)B * kMaxTokens), nt(B);
   int flag = 0;
-  WA_TRY(collect_batch(m, B, gdone, st, tok.data(), nt.data(), &flag));
+  WA_TRY(collect_batch(m, B, false, gdone, st, tok.data(), nt.data(), &flag, 0));
   WA_HIP(hipEventRecord(e_end, st));
   WA_HIP(hipStreamSynchronize(st));
   *overflow = flag != 0;
@@ -200,12 +232,30 @@ wq4_status ensure_enc_stream(wa_model* m) {
 // length over the masked stream's measured time per layer.  Every kernel
 // computes what it computes in wa_transcribe: the same tokens.  flags[i] =
 // batch i's range flag (the caller re-runs flagged batches).
+//
+// Batches of 16 .. 32 clips decode in pairs (see kPairMinClips): the decode
+// step is a chain of dependent launches whose cost barely grows with the
+// rows, so group i of a pair decodes ALL of batch 2p + i (32-row MFMA tiles
+// filled, one pass over the decoder weights and the logits table per 32
+// clips instead of per 16) from lane i of the planes and self-attention
+// caches.  The schedule then runs over units of two batches: beside pair
+// p - 1's decode the masked stream takes the conv stem and first k layers
+// of batch 2p (k adapts as before and may reach L); after that
+// decode the model stream finishes batch 2p's encoder into lane 0 and runs
+// all of batch 2p + 1's into lane 1 (the one set of encoder activations
+// serves both, in turn), and one `ready` event starts both groups.  An odd
+// last batch is a unit of its own on today's groups.  The same four streams
+// as unpaired; a batch's tokens are complete when its unit is.
 wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B, int lang_token, int max_tokens,
                                 int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags) {
   WA_TRY(ensure_enc_stream(m));
   hipStream_t st = m->own_stream, es = m->enc_stream;
-  const int L = (int)m->enc.size(), G = decode_groups(B);
+  const int L = (int)m->enc.size();
   const size_t mel_stride = (size_t)B * m->cfg.n_mels * 2 * m->cfg.n_audio_ctx;
+  // pairs need the encoder-plane groups (not the few-clip K/V caches), the
+  // default two groups per batch and room for the second lane
+  const bool pairing = pair_enabled() && NB >= 2 && B >= kPairMinClips && B <= kPairMaxClips && B > m->kv_small &&
+                       decode_groups(B) == 2 && ensure_pair_lane(m);
   // pinned result staging: per batch the groups' tokens, counts and range flag
   int32_t* host = nullptr;
   const size_t per = (size_t)B * kMaxTokens + B + 1;
@@ -225,29 +275,52 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
     }
   } hg{m, host};
   EventSet ev;
-  struct Batch {
+  // a unit: the batches [first, first + n) decoded by one run_decode
+  struct Unit {
+    int first = 0, n = 1;
     hipEvent_t ready, mstart, mend, pstart, gprompt[kMaxGroups], gdone[kMaxGroups];
-    int k = 0, steps = 0;
+    int k = 0, gsteps[kMaxGroups] = {};
   };
-  std::vector<Batch> bt(NB);
-  for (Batch& b : bt) {
-    for (hipEvent_t* e : {&b.ready, &b.mstart, &b.mend, &b.pstart}) WA_HIP(ev.make(e));
-    for (int i = 0; i < G; ++i) {
-      WA_HIP(ev.make(&b.gprompt[i]));
-      WA_HIP(ev.make(&b.gdone[i]));
+  std::vector<Unit> ut;
+  for (int i = 0; i < NB; i += ut.back().n) {
+    ut.emplace_back();
+    ut.back().first = i;
+    ut.back().n = pairing && NB - i >= 2 ? 2 : 1;
+  }
+  const int NU = (int)ut.size();
+  for (Unit& u : ut) {
+    for (hipEvent_t* e : {&u.ready, &u.mstart, &u.mend, &u.pstart}) WA_HIP(ev.make(e));
+    for (int i = 0; i < unit_groups(B, u.n == 2); ++i) {
+      WA_HIP(ev.make(&u.gprompt[i]));
+      WA_HIP(ev.make(&u.gdone[i]));
     }
   }
+  // On the model stream: the encoder of unit u's batches at full width, each
+  // followed by the planes pass into its lane, then u.ready.  The first
+  // batch continues after the k0 layers the masked stream ran (k0 < 0: none
+  // of it ran, the conv stem neither).
+  auto unit_encoder = [&](Unit& u, int k0) -> wq4_status {
+    for (int j = 0; j < u.n; ++j) {
+      if (j == 0 && k0 >= 0) {
+        WA_TRY(encoder_layers(m, B, k0, L, st));
+        WA_TRY(encoder_post(m, B, st, nullptr));
+      } else {
+        WA_TRY(encoder_forward(m, mel_dev + (u.first + j) * mel_stride, B, st, nullptr));
+      }
+      WA_TRY(cross_kv_forward(m, B, st, true, j));
+    }
+    WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
+    WA_HIP(hipEventRecord(u.ready, st));
+    return WQ4_OK;
+  };
   hipEvent_t e_in, e_enc0;
   WA_HIP(ev.make(&e_in));
   WA_HIP(ev.make(&e_enc0));
   WA_HIP(hipEventRecord(e_in, static_cast<hipStream_t>(stream)));
   WA_HIP(hipStreamWaitEvent(st, e_in, 0));
-  // batch 0: the whole encoder at full width
+  // unit 0: the whole encoder(s) at full width
   WA_HIP(hipEventRecord(e_enc0, st));
-  WA_TRY(encoder_forward(m, mel_dev, B, st, nullptr));
-  WA_TRY(cross_kv_forward(m, B, st, true));
-  WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-  WA_HIP(hipEventRecord(bt[0].ready, st));
+  WA_TRY(unit_encoder(ut[0], -1));
   // the adapted depth belongs to a batch shape: a call with another clip
   // count or EOT mode starts again from the default
   if (m->overlap_k < 0 || m->overlap_b != B || m->overlap_eot != eot_stop) m->overlap_k = std::min(L, kEncOverlapLayers0);
@@ -255,17 +328,19 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
   m->overlap_eot = eot_stop;
   double t_exposed = 0.0, t_masked = 0.0, t_decode = 0.0, t_prompt = 0.0, k_sum = 0.0;
   int32_t steps_all = 0;
-  for (int i = 0; i < NB; ++i) {
-    Batch& b = bt[i];
+  for (int i = 0; i < NU; ++i) {
+    Unit& u = ut[i];
+    const bool pair = u.n == 2;
     if (i >= 1) {
-      // batch i - 1 is decoded (and batch i's masked part done) before batch
-      // i's decode is enqueued: the GPU meanwhile runs batch i's remaining
-      // layers; adapt k to the finished decode
-      Batch& p = bt[i - 1];
-      for (int g = 0; g < G; ++g) WA_HIP(hipEventSynchronize(p.gdone[g]));
+      // unit i - 1 is decoded (and unit i's masked part done) before unit
+      // i's decode is enqueued: the GPU meanwhile runs unit i's remaining
+      // encoder work; adapt k to the finished decode
+      Unit& p = ut[i - 1];
+      const int PG = unit_groups(B, p.n == 2);
+      for (int g = 0; g < PG; ++g) WA_HIP(hipEventSynchronize(p.gdone[g]));
       WA_HIP(hipEventSynchronize(p.mend));
       float td = 0.0f, tm = 0.0f;
-      for (int g = 0; g < G; ++g) {
+      for (int g = 0; g < PG; ++g) {
         float t = 0.0f;
         WA_HIP(hipEventElapsedTime(&t, p.ready, p.gdone[g]));
         td = std::max(td, t);
@@ -279,25 +354,22 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
       }
     }
     if (const char* e = getenv("WA_ENC_OVERLAP")) m->overlap_k = std::max(0, std::min(L, atoi(e)));
-    if (i + 1 < NB) {  // the masked part of batch i + 1, beside batch i's decode
-      b.k = m->overlap_k;
-      WA_HIP(hipStreamWaitEvent(es, b.ready, 0));
-      WA_HIP(hipEventRecord(b.mstart, es));
-      WA_TRY(encoder_front(m, mel_dev + (i + 1) * mel_stride, B, es));
-      WA_TRY(encoder_layers(m, B, 0, b.k, es));
-      WA_HIP(hipEventRecord(b.mend, es));
+    if (i + 1 < NU) {  // the masked part of the next unit's first batch, beside unit i's decode
+      u.k = m->overlap_k;
+      WA_HIP(hipStreamWaitEvent(es, u.ready, 0));
+      WA_HIP(hipEventRecord(u.mstart, es));
+      WA_TRY(encoder_front(m, mel_dev + ut[i + 1].first * mel_stride, B, es));
+      WA_TRY(encoder_layers(m, B, 0, u.k, es));
+      WA_HIP(hipEventRecord(u.mend, es));
     }
-    WA_TRY(run_decode(m, B, lang_token, max_tokens, eot_stop, b.ready, b.gprompt, b.gdone, &b.steps));
-    int32_t* hb = host + (size_t)i * per;
-    WA_TRY(collect_batch(m, B, b.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B));
-    if (i + 1 < NB) {  // the rest of batch i + 1's encoder at full width
-      WA_HIP(hipStreamWaitEvent(st, b.mend, 0));
-      WA_HIP(hipEventRecord(b.pstart, st));
-      WA_TRY(encoder_layers(m, B, b.k, L, st));
-      WA_TRY(encoder_post(m, B, st, nullptr));
-      WA_TRY(cross_kv_forward(m, B, st, true));
-      WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
-      WA_HIP(hipEventRecord(bt[i + 1].ready, st));
+    WA_TRY(run_decode(m, B, pair, lang_token, max_tokens, eot_stop, u.ready, u.gprompt, u.gdone, u.gsteps));
+    int32_t* hb = host + (size_t)u.first * per;
+    WA_TRY(collect_batch(m, B, pair, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
+                         per));
+    if (i + 1 < NU) {  // the rest of the next unit's encoder work at full width
+      WA_HIP(hipStreamWaitEvent(st, u.mend, 0));
+      WA_HIP(hipEventRecord(u.pstart, st));
+      WA_TRY(unit_encoder(ut[i + 1], u.k));
     }
   }
   WA_HIP(hipStreamSynchronize(st));
@@ -307,29 +379,34 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
     copy_tokens(hb, hb + (size_t)B * kMaxTokens, B, max_tokens, tokens_out + (size_t)i * B * max_tokens,
                 n_tokens_out + (size_t)i * B);
     flags[i] = hb[(size_t)B * kMaxTokens + B];
-    // per-batch phases (averaged below)
-    Batch& b = bt[i];
+  }
+  // per-unit phases, averaged over the batches below: a pair's exposed
+  // encoder, prompt and decode times count half for each of its batches
+  for (int i = 0; i < NU; ++i) {
+    Unit& u = ut[i];
+    const int UG = unit_groups(B, u.n == 2);
     float t = 0.0f, tp = 0.0f, td = 0.0f;
     if (i == 0) {
-      WA_HIP(hipEventElapsedTime(&t, e_enc0, b.ready));
+      WA_HIP(hipEventElapsedTime(&t, e_enc0, u.ready));
     } else {
-      WA_HIP(hipEventElapsedTime(&t, bt[i - 1].pstart, b.ready));
+      WA_HIP(hipEventElapsedTime(&t, ut[i - 1].pstart, u.ready));
       float tm = 0.0f;
-      WA_HIP(hipEventElapsedTime(&tm, bt[i - 1].mstart, bt[i - 1].mend));
+      WA_HIP(hipEventElapsedTime(&tm, ut[i - 1].mstart, ut[i - 1].mend));
       t_masked += tm;
-      k_sum += bt[i - 1].k;
+      k_sum += ut[i - 1].k;
     }
     t_exposed += t;
-    for (int g = 0; g < G; ++g) {
+    for (int g = 0; g < UG; ++g) {
       float a = 0.0f, d = 0.0f;
-      WA_HIP(hipEventElapsedTime(&a, b.ready, b.gprompt[g]));
-      WA_HIP(hipEventElapsedTime(&d, b.ready, b.gdone[g]));
+      WA_HIP(hipEventElapsedTime(&a, u.ready, u.gprompt[g]));
+      WA_HIP(hipEventElapsedTime(&d, u.ready, u.gdone[g]));
       tp = std::max(tp, a);
       td = std::max(td, d);
     }
     t_prompt += tp;
     t_decode += td - tp;
-    steps_all += b.steps;
+    // steps of a batch: its group's in a pair, else the last group's to stop
+    steps_all += u.n == 2 ? u.gsteps[0] + u.gsteps[1] : *std::max_element(u.gsteps, u.gsteps + UG);
   }
   m->timings[0] = (float)(t_exposed / NB);
   m->timings[1] = 0.0f;
@@ -337,9 +414,10 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
   m->timings[3] = (float)(t_decode / NB);
   m->timings[4] = (float)steps_all / NB;
   m->pipe[0] = (float)NB;
-  m->pipe[1] = NB > 1 ? (float)(k_sum / (NB - 1)) : 0.0f;
-  m->pipe[2] = NB > 1 ? (float)(t_masked / (NB - 1)) : 0.0f;
+  m->pipe[1] = NU > 1 ? (float)(k_sum / (NU - 1)) : 0.0f;  // per masked part
+  m->pipe[2] = NU > 1 ? (float)(t_masked / (NU - 1)) : 0.0f;
   m->pipe[3] = (float)m->enc_cus;
+  m->pipe_pairs = pairing ? NB / 2 : 0;
   return WQ4_OK;
 }
 
@@ -404,6 +482,8 @@ wq4_status wa_last_pipeline_stats(const wa_model* m, float* out) {
   return WQ4_OK;
 }
 
+int wa_last_pipeline_pairs(const wa_model* m) { return m ? m->pipe_pairs : 0; }
+
 wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const int32_t* trace_ids_dev,
                                int trace_k, float* trace_out_dev, void* stream) {
@@ -418,9 +498,11 @@ wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, i
   m->trace_out = nullptr;
   m->trace_s1 = m->trace_k = 0;
   for (DecGroup& g : m->groups) {  // the trace graphs bake in the caller's buffers: never replay them again
-    if (g.graph) (void)hipGraphExecDestroy(g.graph);
-    g.graph = nullptr;
-    g.graph_key = -1;
+    for (hipGraphExec_t* x : {&g.graph, &g.graph_alt}) {
+      if (*x) (void)hipGraphExecDestroy(*x);
+      *x = nullptr;
+    }
+    g.graph_key = g.graph_alt_key = -1;
   }
   return s;
 }

@@ -43,6 +43,8 @@ def lib() -> ctypes.CDLL:
         L.wa_last_timings.argtypes = [vp, f32p]
         L.wa_transcribe_batches.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, vp]
         L.wa_last_pipeline_stats.argtypes = [vp, f32p]
+        L.wa_last_pipeline_pairs.argtypes = [vp]
+        L.wa_last_pipeline_pairs.restype = c_int
         L.wa_encode.argtypes = [vp, vp, c_int, vp, vp]
         L.wa_prompt_logits.argtypes = [vp, vp, c_int, c_int, vp, vp]
         L.wa_synth_uniform.argtypes = [ctypes.c_uint64, ctypes.c_char_p, c_i64, ctypes.c_float, ctypes.c_float, f32p]
@@ -352,6 +354,11 @@ class WhisperModel:
         t = (ctypes.c_float * 4)()
         check(lib().wa_last_pipeline_stats(self._h, t))
         return {"batches": int(t[0]), "overlap_layers": t[1], "masked_ms": t[2], "masked_cus": int(t[3])}
+
+    def pipeline_pairs(self) -> int:
+        """Batch pairs the last transcribe_batches decoded together, one decode
+        group per batch (wa_last_pipeline_pairs); 0: every batch on its own."""
+        return int(lib().wa_last_pipeline_pairs(self._h))
 
     def transcribe_trace(self, mel, trace_ids: np.ndarray, lang_token: Optional[int] = 50259,
                          max_tokens: int = 224, eot_stop: bool = False):
