@@ -51,10 +51,35 @@ wq4_status wa_xattn_check(int device, const float* q_dev, const uint8_t* wk_dev,
     if (!wvp) return fail(WQ4_ENOMEM, "allocation failed");
     WA_HIP(launch_wv_pack(wv_dev, H, D, wvp, nullptr));
   }
+  // the policy of a decode with these clips live (WA_XATTN_RESIDENT_MB: the tests force each share)
+  const XattnResidency res = xattn_residency(n_clips, T, ns, D);
   return tiled_check(d, R, D, prec, out_dev, [&](_Float16* tiled) {
     return launch_xattn(q_dev, wk_dev, wv_dev, wvp, bv_dev, weight_type, enc, n_clips, Tq, T, H, D, qt, part, tiled,
-                        ns, nullptr);
+                        ns, res, nullptr);
   });
+}
+
+int wa_xattn_resident_share(int live_clips, int T, int planes, int D, double budget_mb) {
+  if (live_clips < 1 || T < 1 || planes < 1 || planes > 2 || D < 1) return -1;
+  return xattn_residency(live_clips, T, planes, D, budget_mb).q;
+}
+
+int wa_xattn_chunk_resident(int chunk, int share) {
+  if (chunk < 0 || share < 0 || share > kXattnResDen) return -1;
+  return xattn_chunk_resident(chunk, share) ? 1 : 0;
+}
+
+wq4_status wa_xattn_plan(int T, int* splits, int* chunks_per_split) {
+  if (T < 1 || !splits || !chunks_per_split) return fail(WQ4_EINVAL, "bad arguments");
+  const XattnPlan p = xattn_plan(1, T);
+  *splits = p.splits;
+  *chunks_per_split = p.ch;
+  return WQ4_OK;
+}
+
+long long wa_decode_graph_key(const wa_model* m, int group) {
+  if (!m || group < 0 || group >= (int)m->groups.size()) return -1;
+  return m->groups[group].graph_key;
 }
 
 wq4_status wa_xattn_kv_check(int device, const float* q_dev, const float* k_dev, const float* v_dev, int n_clips,

@@ -61,10 +61,28 @@ size_t xattn_part_floats(int R, int H, int D, int T);
 // projection's lane order (same bytes; wv_pack_words u32 words).
 size_t wv_pack_words(int H, int D);
 hipError_t launch_wv_pack(const uint8_t* wv, int H, int D, uint32_t* out, hipStream_t st);
+// Infinity Cache residency of the encoder planes: of every kXattnResDen
+// consecutive 16-frame sub-chunks of a clip, q load with the default cache
+// policy (and stay on-die from one decoder layer to the next), the others
+// nontemporal.  q = kXattnResDen: everything default.  Values never change.
+constexpr int kXattnResDen = 64;
+struct XattnResidency {
+  int q = kXattnResDen;
+};
+// The one predicate of every kernel that reads the planes: a fixed function
+// of the clip's sub-chunk index (never of step, layer, group or split), so a
+// line always loads with the same policy.  Residents are evenly interleaved:
+// any n consecutive sub-chunks hold floor or ceil(n q / 64) of them, so every
+// (row, split) workgroup of a launch walks the same mix.
+constexpr bool xattn_chunk_resident(int chunk, int q) { return ((chunk * q) & (kXattnResDen - 1)) + q >= kXattnResDen; }
+// The share for a decode whose concurrently running groups stream the planes
+// of live_clips clips in all ([T][ns][D] f16 each); budget_mb < 0: the
+// product's rule, else a budget in MB (10^6 bytes) that replaces it.
+XattnResidency xattn_residency(int live_clips, int T, int ns, int D, double budget_mb = -1.0);
 // wvp: the launch_wv_pack words of wv (Q4 weights; ignored for f16 weights).
 hipError_t launch_xattn(const float* q, const uint8_t* wk, const uint8_t* wv, const uint32_t* wvp, const float* bv,
                         int wtype, const _Float16* enc, int B, int Tq, int T, int H, int D, _Float16* qt, float* part,
-                        _Float16* tiled, int ns, hipStream_t st, float* out32 = nullptr);
+                        _Float16* tiled, int ns, XattnResidency res, hipStream_t st, float* out32 = nullptr);
 // A-tiled operand [R][K] (hi + lo) -> f32 rows (diagnostics).
 hipError_t launch_untile(const _Float16* tiled, int R, int K, int ns, float* out, hipStream_t st);
 // f32 rows [rows][D] -> [rows][ns][D] f16 planes (hi | lo) for launch_xattn.

@@ -112,6 +112,10 @@ struct DecGroup {
   hipStream_t st = nullptr;
   int b0 = 0, nb = 0;
   int lane = 0;
+  // cache residency of the encoder planes for the decode this group is part
+  // of (run_decode: from the clips of every group that decodes beside it);
+  // baked into the captured step graph
+  XattnResidency xres;
   float *xd, *qkvd, *qd, *hid, *logits;
   _Float16 *atd_dec, *atf_dec;
   int *prompt_tok, *next_tok, *tokens, *ntok, *done;
@@ -129,7 +133,7 @@ struct DecGroup {
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace) the graph was captured for
+  int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace, plane residency) the graph was captured for
   hipGraphExec_t graph_alt = nullptr;  // the graph `graph` replaced last (ensure_graph)
   int64_t graph_alt_key = -1;
 };

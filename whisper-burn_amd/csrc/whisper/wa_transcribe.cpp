@@ -66,8 +66,12 @@ int unit_groups(int B, bool pair) { return pair ? 2 : decode_groups(B); }
 wq4_status run_decode(wa_model* m, int B, bool pair, int lang_token, int max_tokens, int eot_stop, hipEvent_t ready,
                       const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps) {
   const int G = unit_groups(B, pair);
+  // the groups decode concurrently: the planes of all their clips are live
+  // (both lanes of a pair), which decides the share each keeps cached
+  const XattnResidency xres = xattn_residency(pair ? 2 * B : B, m->cfg.n_audio_ctx, m->ns, m->cfg.n_audio_state);
   for (int i = 0; i < G; ++i) {
     DecGroup& g = m->groups[i];
+    g.xres = xres;
     g.lane = pair ? i : 0;
     g.b0 = pair ? 0 : (int)((int64_t)B * i / G);
     g.nb = pair ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;

@@ -77,16 +77,20 @@ constexpr int kXattnSplits = WA_XATTN_SPLITS;
 #ifndef WA_XATTN_DIAG
 #define WA_XATTN_DIAG 0
 #endif
-// Frames whose encoder-plane sub-chunks xattn_main loads with the default
-// cache policy; the rest use WA_XATTN_STREAM_AUX (nontemporal).  >= 1500:
-// all default (tuning builds: scripts/gpu.sh libs).
-#ifndef WA_XATTN_CACHE_FRAMES
-#define WA_XATTN_CACHE_FRAMES 1500
-#endif
+// Cache policy of the encoder-plane sub-chunks that are not resident
+// (xattn_chunk_resident, wa_kernels.hpp): buffer-load aux 2 = nontemporal.
 #ifndef WA_XATTN_STREAM_AUX
 #define WA_XATTN_STREAM_AUX 2
 #endif
-constexpr int kMaxFrames = 1500;
+// Z partials (xattn_main -> xattn_out, written and read exactly once, 26 MB
+// per 32-row group and layer, so 52 MB pass through the cache between two
+// uses of a plane line of a pair): bit 0 = nontemporal stores in xattn_main,
+// bit 1 = nontemporal loads in xattn_out (tuning builds: scripts/gpu.sh
+// libs).  Paired bench at a resident share of 0.4, RTF: 1178 with neither,
+// 1181 stores only, 1190 loads only, 1192 both (profiles/resident_sweep.json).
+#ifndef WA_XATTN_ZPART_NT
+#define WA_XATTN_ZPART_NT 3
+#endif
 // WA_XATTN_STAMP (tools/xattn_micro.hip only): the clock at the phase
 // boundaries of every sub-chunk of workgroup (0, 0), waves 0 and NW - 1,
 // into g_xstamp (read back with hipMemcpyFromSymbol; results unchanged).
@@ -251,11 +255,14 @@ __device__ __forceinline__ void softmax_entry(float sv, bool valid, float& M, fl
 // heads, k = the 16 frames read transposed from the same LDS image by
 // ds_read_b64_tr_b16; accumulators stay in registers).  Writes per (row,
 // split): Z [H][D] and (max, sum) [H].
-template <int D, int HT, int NS, int NW, int PF>
+// POL = false: every sub-chunk loads with the default cache policy (no
+// branch); true: sub-chunk c of the clip is resident iff
+// xattn_chunk_resident(c, resq), the others load nontemporal.
+template <int D, int HT, int NS, int NW, int PF, bool POL>
 __global__ __launch_bounds__(64 * NW) void xattn_main_kernel(const _Float16* __restrict__ qt,
                                                              const _Float16* __restrict__ enc, int Tq, int T,
                                                              int H, int S, int CH, float* __restrict__ zpart,
-                                                             float* __restrict__ mlpart, int R) {
+                                                             float* __restrict__ mlpart, int R, int resq) {
   constexpr int kThreads = 64 * NW;
   constexpr int CW = D / NW;      // columns per wave
   constexpr int KS = CW / 32;     // 32-column steps per wave (score k-steps = Z column tiles)
@@ -348,12 +355,12 @@ __global__ __launch_bounds__(64 * NW) void xattn_main_kernel(const _Float16* __r
     row = rem / PPR;
     col = p * D + c0 + (rem - row * PPR) * 8;
   };
-  // Infinity Cache policy (WA_XATTN_CACHE_FRAMES): the sub-chunks of frames
-  // below the bound load with the default policy, the rest nontemporal, so
-  // that the part of every clip's planes that fits stays cached from one
-  // layer to the next instead of the whole set thrashing it (both decode
-  // groups' planes, 245 MB at 32 clips, against 256 MB).  Same values either
-  // way; one wave-uniform branch per sub-chunk.
+  // Infinity Cache policy (xattn_residency): when the planes of every clip
+  // that decodes concurrently exceed the cache (a pair: 2 x 245.8 MB against
+  // 256 MiB) a fixed set of each clip's sub-chunks loads with the default
+  // policy and stays cached from one layer to the next; the rest load
+  // nontemporal and stream past it instead of the whole set thrashing it.
+  // Same values either way; one wave-uniform branch per sub-chunk.
   auto fetch_aux = [&](u32x4v(&buf)[NLD], int chi, auto aux_c) {
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -364,7 +371,7 @@ __global__ __launch_bounds__(64 * NW) void xattn_main_kernel(const _Float16* __r
     }
   };
   auto fetch = [&](u32x4v (&buf)[NLD], int chi) {
-    if (WA_XATTN_CACHE_FRAMES >= kMaxFrames || ts + chi * kTc < WA_XATTN_CACHE_FRAMES)
+    if (!POL || xattn_chunk_resident(s * CH + chi, resq))
       fetch_aux(buf, chi, std::integral_constant<int, 0>{});
     else
       fetch_aux(buf, chi, std::integral_constant<int, WA_XATTN_STREAM_AUX>{});
@@ -542,7 +549,13 @@ __global__ __launch_bounds__(64 * NW) void xattn_main_kernel(const _Float16* __r
     const int h = (j & 3) + 8 * (j >> 2) + 4 * lh;
     if (h < H) {
 #pragma unroll
-      for (int ct = 0; ct < KS; ++ct) zpart[(base * H + h) * D + c0 + ct * 32 + l32] = zacc[ct][j] * kZInv;
+      for (int ct = 0; ct < KS; ++ct) {
+        float* zp = &zpart[(base * H + h) * D + c0 + ct * 32 + l32];
+        if (WA_XATTN_ZPART_NT & 1)
+          __builtin_nontemporal_store(zacc[ct][j] * kZInv, zp);
+        else
+          *zp = zacc[ct][j] * kZInv;
+      }
     }
   }
 }
@@ -654,7 +667,10 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
       const floatx4* zp = reinterpret_cast<const floatx4*>(zpart + (rb * H + h) * D) + (ok ? q : 0);
 #pragma unroll
       for (int s = 0; s < SM; ++s)
-        if (s < S) zv[u][s] = WA_XATTN_ODIAG == 2 ? floatx4{0.0f, 0.0f, 0.0f, 0.0f} : zp[(size_t)s * H * (D / 4)];
+        if (s < S)
+          zv[u][s] = WA_XATTN_ODIAG == 2         ? floatx4{0.0f, 0.0f, 0.0f, 0.0f}
+                     : (WA_XATTN_ZPART_NT & 2) ? __builtin_nontemporal_load(&zp[(size_t)s * H * (D / 4)])
+                                               : zp[(size_t)s * H * (D / 4)];
     }
     if (tid < RPW) {
       const int j = tid;
@@ -850,7 +866,7 @@ constexpr int kSmallRowsMax = 8;  // scratch is sized for up to this many rows
 template <int D, int HT, int NS, int NW>
 __global__ __launch_bounds__(64 * NW) void xattn_scores_kernel(const _Float16* __restrict__ qt,
                                                                const _Float16* __restrict__ enc, int Tq, int T,
-                                                               int NG, float* __restrict__ sbuf) {
+                                                               int NG, float* __restrict__ sbuf, int resq) {
   constexpr int CW = D / NW, KS = CW / 32, HP = HT * 16, ROW = NS * D;
   __shared__ __attribute__((aligned(16))) float red[NW][HT][16][20];
   const int g = blockIdx.x, r = blockIdx.y;
@@ -862,11 +878,18 @@ __global__ __launch_bounds__(64 * NW) void xattn_scores_kernel(const _Float16* _
   // tile's padding lanes zero
   half8 a[KS][NS];
   const int fc = f < T ? f : T - 1;
+  const half8* ap = reinterpret_cast<const half8*>(E + (size_t)fc * ROW + c0 + 8 * lq);
+  if (xattn_chunk_resident(g, resq)) {  // the fused kernel's policy for sub-chunk g (workgroup-uniform)
 #pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
+    for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-    for (int p = 0; p < NS; ++p)
-      a[ks][p] = *reinterpret_cast<const half8*>(E + (size_t)fc * ROW + p * D + c0 + ks * 32 + 8 * lq);
+      for (int p = 0; p < NS; ++p) a[ks][p] = ap[(p * D + ks * 32) / 8];
+  } else {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+      for (int p = 0; p < NS; ++p) a[ks][p] = __builtin_nontemporal_load(&ap[(p * D + ks * 32) / 8]);
+  }
   if (f >= T) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
@@ -924,7 +947,7 @@ template <int D, int HT, int NS>
 __global__ __launch_bounds__(256) void xattn_z_kernel(const _Float16* __restrict__ enc,
                                                       const float* __restrict__ sbuf, int Tq, int T, int H, int S,
                                                       int CH, int NG, float* __restrict__ zpart,
-                                                      float* __restrict__ mlpart) {
+                                                      float* __restrict__ mlpart, int resq) {
   constexpr int ROW = NS * D, ZR = 32, HP = HT * 16;  // staged plane: 16 frames x 32 columns, rows of 64 B
   constexpr int SMX = 512 / 256;                      // softmax entries (head 0..31, frame) per thread
   __shared__ __attribute__((aligned(16))) _Float16 sp[kSmallMaxCH][NS][32][kTc];
@@ -945,11 +968,17 @@ __global__ __launch_bounds__(256) void xattn_z_kernel(const _Float16* __restrict
       const_cast<_Float16*>(E + (size_t)ts * ROW), 0, nch > 0 ? (te - ts) * ROW * 2 : 0, 0x00020000);
   u32x4v ev[kSmallMaxCH][NS];
 #pragma unroll
-  for (int c = 0; c < kSmallMaxCH; ++c)
+  for (int c = 0; c < kSmallMaxCH; ++c) {  // unconditional: past the split's frames the buffer gives zeros
+    const uint32_t eo = (uint32_t)((((c * kTc + (l >> 2)) * ROW) + cb + 8 * (l & 3)) * 2);
+    if (xattn_chunk_resident(s * CH + c, resq)) {  // the fused kernel's policy for the sub-chunk
 #pragma unroll
-    for (int p = 0; p < NS; ++p)  // unconditional: past the split's frames the buffer gives zeros
-      ev[c][p] = __builtin_amdgcn_raw_buffer_load_b128(
-          rs, (uint32_t)((((c * kTc + (l >> 2)) * ROW) + p * D + cb + 8 * (l & 3)) * 2), 0, 0);
+      for (int p = 0; p < NS; ++p) ev[c][p] = __builtin_amdgcn_raw_buffer_load_b128(rs, eo + p * D * 2, 0, 0);
+    } else {
+#pragma unroll
+      for (int p = 0; p < NS; ++p)
+        ev[c][p] = __builtin_amdgcn_raw_buffer_load_b128(rs, eo + p * D * 2, 0, WA_XATTN_STREAM_AUX);
+    }
+  }
   // the split's scores (every load issued up front)
   float sv_all[kSmallMaxCH][SMX];
 #pragma unroll
@@ -1041,13 +1070,14 @@ __global__ __launch_bounds__(256) void xattn_z_kernel(const _Float16* __restrict
 
 template <int D, int HT, int NS>
 void launch_small(int R, int Tq, int T, int H, const XattnPlan& p, const _Float16* qt, const _Float16* enc,
-                  float* z, float* ml, float* scratch, hipStream_t st) {
+                  float* z, float* ml, float* scratch, int resq, hipStream_t st) {
   constexpr int NW = (D / 8) % 32 == 0 ? 8 : 4;
   const int NG = p.splits * p.ch;
   float* sb = scratch;  // R * NG * 32 * 16 floats
-  hipLaunchKernelGGL((xattn_scores_kernel<D, HT, NS, NW>), dim3(NG, R), dim3(64 * NW), 0, st, qt, enc, Tq, T, NG, sb);
+  hipLaunchKernelGGL((xattn_scores_kernel<D, HT, NS, NW>), dim3(NG, R), dim3(64 * NW), 0, st, qt, enc, Tq, T, NG, sb,
+                     resq);
   hipLaunchKernelGGL((xattn_z_kernel<D, HT, NS>), dim3(p.splits, D / 128, R), dim3(256), 0, st, enc, sb, Tq, T, H,
-                     p.splits, p.ch, NG, z, ml);
+                     p.splits, p.ch, NG, z, ml, resq);
 }
 
 // Query rows at or below which the split phases run (WA_XATTN_SMALL_ROWS
@@ -1067,10 +1097,14 @@ int xattn_small_rows() {
 // interleaved) -- 45.3 vs 36.2 us at 16 rows, decode 970 vs 856 ms.
 template <int D, int HT, int NS>
 void launch_main(dim3 g, const _Float16* qt, const _Float16* enc, int Tq, int T, int H, int S, int CH, float* z,
-                 float* ml, int R, hipStream_t st) {
+                 float* ml, int R, int resq, hipStream_t st) {
   constexpr int NW = (D / 8) % 32 == 0 ? 8 : 4;
-  hipLaunchKernelGGL((xattn_main_kernel<D, HT, NS, NW, 1>), g, dim3(64 * NW), 0, st, qt, enc, Tq, T, H, S, CH, z, ml,
-                     R);
+  if (resq >= kXattnResDen)  // everything resident: the kernel without the policy branch
+    hipLaunchKernelGGL((xattn_main_kernel<D, HT, NS, NW, 1, false>), g, dim3(64 * NW), 0, st, qt, enc, Tq, T, H, S,
+                       CH, z, ml, R, resq);
+  else
+    hipLaunchKernelGGL((xattn_main_kernel<D, HT, NS, NW, 1, true>), g, dim3(64 * NW), 0, st, qt, enc, Tq, T, H, S, CH,
+                       z, ml, R, resq);
 }
 
 // Rows of Zn per xattn_out workgroup: 4.  Isolated, 2 rows per workgroup is
@@ -1127,6 +1161,39 @@ XattnPlan xattn_plan(int R, int T) {
   return p;
 }
 
+// Which share of every clip's planes stays in the Infinity Cache (DESIGN.md
+// section 10, "plane residency").  live_clips: every clip whose planes a
+// concurrently running decode group streams (all lanes and groups: 64 for a
+// pair).  While the live planes fit the cache they are all resident (the
+// measured best at <= 32 Large-V3 clips); beyond it the planes that load with
+// the default policy are held to a byte budget -- what the cache keeps beside
+// everything else the decode moves through it between two uses of a line
+// (activations, weights, the masked encoder) -- so the share follows from the
+// clip count, T and the model width.  The budget is the best point of the
+// paired bench's sweep (profiles/resident_sweep.json: RTF 1184 / 1193 / 1190
+// / 1189 / 1178 at 0.25 / 0.35 / 0.4 / 0.45 / 0.5 of a pair's 491.5 MB, 1156
+// at 0 and at 1).  WA_XATTN_RESIDENT_MB (A/B runs and tests only) replaces
+// both bounds: 0 = all nontemporal, large = all default.
+constexpr double kXattnFitMB = 268.4;       // 256 MiB
+constexpr double kXattnResidentMB = 172.0;  // 0.35 of a pair's planes
+XattnResidency xattn_residency(int live_clips, int T, int ns, int D, double budget_mb) {
+  const double live = (double)live_clips * T * ns * D * 2.0;
+  double fit = kXattnFitMB;
+  if (budget_mb < 0.0) {
+    budget_mb = kXattnResidentMB;
+    if (const char* e = getenv("WA_XATTN_RESIDENT_MB")) budget_mb = fit = std::max(0.0, atof(e));
+  } else {
+    fit = budget_mb;
+  }
+  XattnResidency r;
+  const double budget = std::min(budget_mb, 1e9) * 1e6;
+  if (live <= std::max(fit * 1e6, budget))
+    r.q = kXattnResDen;
+  else
+    r.q = std::max(0, std::min(kXattnResDen - 1, (int)std::floor(kXattnResDen * budget / live)));
+  return r;
+}
+
 size_t xattn_part_floats(int R, int H, int D, int T) {
   const XattnPlan p = xattn_plan(R, T);
   size_t n = (size_t)R * p.splits * H * ((size_t)D + 2) + (size_t)R * H * D;
@@ -1167,10 +1234,11 @@ hipError_t launch_wv_pack(const uint8_t* wv, int H, int D, uint32_t* out, hipStr
 
 hipError_t launch_xattn(const float* q, const uint8_t* wk, const uint8_t* wv, const uint32_t* wvp, const float* bv,
                         int wtype, const _Float16* enc, int B, int Tq, int T, int H, int D, _Float16* qt, float* part,
-                        _Float16* tiled, int ns, hipStream_t st, float* out32) {
+                        _Float16* tiled, int ns, XattnResidency res, hipStream_t st, float* out32) {
   const int R = B * Tq;
   const int HT = (H + 15) / 16, HP = HT * 16;
   if (D != H * 64 || D % 128 != 0 || D > kMaxD || H > 20 || !q) return hipErrorInvalidValue;
+  if (res.q < 0 || res.q > kXattnResDen) return hipErrorInvalidValue;
   if (wtype == kWtQ4 && !wvp) return hipErrorInvalidValue;  // Q4: the load-time packed Wv (launch_wv_pack)
   const XattnPlan p = xattn_plan(R, T);
   float* z = part;
@@ -1192,13 +1260,13 @@ hipError_t launch_xattn(const float* q, const uint8_t* wk, const uint8_t* wv, co
   if (D == DD && HT == HH) {                                                               \
     if (small) {                                                                           \
       if (ns == 2)                                                                         \
-        launch_small<DD, HH, 2>(R, Tq, T, H, p, qt, enc, z, ml, scratch, st);              \
+        launch_small<DD, HH, 2>(R, Tq, T, H, p, qt, enc, z, ml, scratch, res.q, st);       \
       else                                                                                 \
-        launch_small<DD, HH, 1>(R, Tq, T, H, p, qt, enc, z, ml, scratch, st);              \
+        launch_small<DD, HH, 1>(R, Tq, T, H, p, qt, enc, z, ml, scratch, res.q, st);       \
     } else if (ns == 2)                                                                    \
-      launch_main<DD, HH, 2>(gm, qt, enc, Tq, T, H, p.splits, p.ch, z, ml, R, st);          \
+      launch_main<DD, HH, 2>(gm, qt, enc, Tq, T, H, p.splits, p.ch, z, ml, R, res.q, st);  \
     else                                                                                   \
-      launch_main<DD, HH, 1>(gm, qt, enc, Tq, T, H, p.splits, p.ch, z, ml, R, st);          \
+      launch_main<DD, HH, 1>(gm, qt, enc, Tq, T, H, p.splits, p.ch, z, ml, R, res.q, st);  \
   } else
   WA_XMAIN(1280, 2)
   WA_XMAIN(1024, 1)

@@ -85,7 +85,7 @@ int main(int argc, char** argv) {
       return ms * 1e3f / iters;
     };
     const float t_main = time_it([&] {
-      wa::launch_main<1280, 2, 2>(dim3(p.splits, R), qt, enc, 1, T, H, p.splits, p.ch, z, ml, R, 0);
+      wa::launch_main<1280, 2, 2>(dim3(p.splits, R), qt, enc, 1, T, H, p.splits, p.ch, z, ml, R, wa::kXattnResDen, 0);
     });
     const float t_q = time_it([&] {
       hipLaunchKernelGGL((wa::xattn_q_mfma_kernel<2, wa::kWtQ4>), dim3(H, D / 64, (R + 31) / 32), dim3(128), 0, 0,
@@ -99,25 +99,26 @@ int main(int argc, char** argv) {
     });
     printf("{\"rows\": %d, \"out_split4_us\": %.2f}\n", R, t_out4);
     const float t_all = time_it([&] {
-      wa::launch_xattn(q, wk, wv, wvp, bv, wa::kWtQ4, enc, R, 1, T, H, D, qt, part, tiled, NS, 0);
+      wa::launch_xattn(q, wk, wv, wvp, bv, wa::kWtQ4, enc, R, 1, T, H, D, qt, part, tiled, NS, wa::XattnResidency{}, 0);
     });
     float t_sc = 0.0f, t_z = 0.0f;
     if (R <= wa::kSmallRowsMax) {  // the split phases one by one
       const int NG = p.splits * p.ch;
       float* sb = part + ((size_t)R * p.splits * H * ((size_t)D + 2) + (size_t)R * H * D + 3) / 4 * 4;
       t_sc = time_it([&] {
-        hipLaunchKernelGGL((wa::xattn_scores_kernel<1280, 2, 2, 8>), dim3(NG, R), dim3(512), 0, 0, qt, enc, 1, T, NG, sb);
+        hipLaunchKernelGGL((wa::xattn_scores_kernel<1280, 2, 2, 8>), dim3(NG, R), dim3(512), 0, 0, qt, enc, 1, T, NG, sb,
+                           wa::kXattnResDen);
       });
       t_z = time_it([&] {
         hipLaunchKernelGGL((wa::xattn_z_kernel<1280, 2, 2>), dim3(p.splits, D / 128, R), dim3(256), 0, 0, enc, sb, 1, T,
-                           H, p.splits, p.ch, NG, z, ml);
+                           H, p.splits, p.ch, NG, z, ml, wa::kXattnResDen);
       });
     }
     CK(hipGetLastError());
 #if WA_XATTN_STAMP
     {  // phase durations of workgroup (0, 0) in the last timed main launch (clock cycles)
       (void)time_it([&] {
-        wa::launch_main<1280, 2, 2>(dim3(p.splits, R), qt, enc, 1, T, H, p.splits, p.ch, z, ml, R, 0);
+        wa::launch_main<1280, 2, 2>(dim3(p.splits, R), qt, enc, 1, T, H, p.splits, p.ch, z, ml, R, wa::kXattnResDen, 0);
       });
       unsigned long long st[2][wa::kXsChunks][wa::kXsPhases];
       CK(hipMemcpyFromSymbol(st, HIP_SYMBOL(wa::g_xstamp), sizeof(st)));

@@ -74,6 +74,14 @@ def lib() -> ctypes.CDLL:
         L.wa_log_mel.argtypes = [c_int, vp, c_int, c_i64, c_i64, c_int, vp, vp]
         L.wa_mel_filterbank.argtypes = [c_int, f32p, f32p]
         L.wa_xattn_check.argtypes = [c_int, vp, vp, vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, vp]
+        L.wa_xattn_resident_share.argtypes = [c_int, c_int, c_int, c_int, ctypes.c_double]
+        L.wa_xattn_resident_share.restype = c_int
+        L.wa_xattn_chunk_resident.argtypes = [c_int, c_int]
+        L.wa_xattn_chunk_resident.restype = c_int
+        L.wa_xattn_plan.argtypes = [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        L.wa_xattn_plan.restype = c_int
+        L.wa_decode_graph_key.argtypes = [vp, c_int]
+        L.wa_decode_graph_key.restype = ctypes.c_longlong
         L.wa_xattn_kv_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
         L.wa_transcribe_trace.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, vp, c_int, vp, vp]
         L.wa_encoder_attention_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, vp]
@@ -160,6 +168,34 @@ def xattn_check(q, wk_raw, wv_raw, bv, enc, Tq: int, H: int, weight_type: int = 
     check(lib().wa_xattn_check(dev, ptr(q), ptr(wk_raw), ptr(wv_raw), ptr(bv), weight_type, ptr(enc), B, Tq, T, H,
                                precision, ptr(out)))
     return out
+
+
+XATTN_SHARE_DEN = 64  # wa_xattn_resident_share counts 64ths of a clip's sub-chunks
+
+
+def xattn_resident_share(live_clips: int, T: int, planes: int, D: int, budget_mb: float = -1.0) -> int:
+    """64ths of every clip's encoder-plane sub-chunks a decode with live_clips
+    clips live keeps in the Infinity Cache (wa_xattn_resident_share; host
+    logic): budget_mb < 0 = the product's rule."""
+    q = int(lib().wa_xattn_resident_share(live_clips, T, planes, D, budget_mb))
+    if q < 0:
+        raise ValueError("bad sizes")
+    return q
+
+
+def xattn_chunk_resident(chunk: int, share: int) -> bool:
+    """Whether 16-frame sub-chunk `chunk` of a clip is resident at `share` 64ths."""
+    r = int(lib().wa_xattn_chunk_resident(chunk, share))
+    if r < 0:
+        raise ValueError("bad chunk / share")
+    return bool(r)
+
+
+def xattn_plan(T: int) -> tuple[int, int]:
+    """(splits, sub-chunks per split) of the cross-attention's frame split for T frames."""
+    s, c = ctypes.c_int(), ctypes.c_int()
+    check(lib().wa_xattn_plan(T, ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
 
 
 def xattn_kv_check(q, k, v, Tq: int, precision: int = wq4.PREC_F16X2):
@@ -359,6 +395,10 @@ class WhisperModel:
         """Batch pairs the last transcribe_batches decoded together, one decode
         group per batch (wa_last_pipeline_pairs); 0: every batch on its own."""
         return int(lib().wa_last_pipeline_pairs(self._h))
+
+    def decode_graph_key(self, group: int = 0) -> int:
+        """Key of decode group `group`'s current step graph (wa_decode_graph_key; -1: none)."""
+        return int(lib().wa_decode_graph_key(self._h, group))
 
     def transcribe_trace(self, mel, trace_ids: np.ndarray, lang_token: Optional[int] = 50259,
                          max_tokens: int = 224, eot_stop: bool = False):
