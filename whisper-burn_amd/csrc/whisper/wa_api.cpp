@@ -185,6 +185,7 @@ wq4_status wa_prompt_logits(wa_model* m, const int32_t* prompt_dev, int n_clips,
   g.b0 = 0;
   g.nb = n_clips;
   g.xres = xattn_residency(n_clips, m->cfg.n_audio_ctx, m->ns, m->cfg.n_audio_state);
+  g.xplan = xattn_plan(m->cfg.n_audio_ctx, n_clips);
   WA_TRY(decoder_forward(m, g, prompt_dev, plen, nullptr, 0, 0, st));
   WA_HIP(hipMemcpyAsync(logits_dev, g.logits, (size_t)n_clips * m->cfg.n_vocab * 4, hipMemcpyDeviceToDevice, st));
   return WQ4_OK;
@@ -221,11 +222,12 @@ wq4_status wa_probe_kernels(wa_model* m, int n_clips, int iters, double* out, in
   g.nb = B;
   const bool kv = m->group_kv(g);
   const XattnResidency res = xattn_residency(B, T, m->ns, D);  // the launch alone: its own clips are all that is live
+  const XattnPlan plan = xattn_plan(T, B);                     // and nothing runs beside it
   auto xattn = [&]() -> hipError_t {
     if (kv)
       return launch_cross_attention_kv(g.qd, L.xk, L.xv, B, 1, T, H, g.xkv_part, g.xkv_ctr, g.atd_dec, m->ns, st);
     return launch_xattn(g.qd, L.ck_raw, L.cv_raw, L.cv_p, L.cv_b, m->wtype, enc, B, 1, T, H, D, g.xqt, g.xattn_part,
-                        g.atd_dec, m->ns, res, st);
+                        g.atd_dec, m->ns, res, plan, st);
   };
   WA_HIP(xattn());
   WA_HIP(hipEventRecord(a, st));

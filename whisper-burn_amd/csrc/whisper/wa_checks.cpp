@@ -53,9 +53,11 @@ wq4_status wa_xattn_check(int device, const float* q_dev, const uint8_t* wk_dev,
   }
   // the policy of a decode with these clips live (WA_XATTN_RESIDENT_MB: the tests force each share)
   const XattnResidency res = xattn_residency(n_clips, T, ns, D);
+  // nothing runs beside the launch: the default plan (WA_XATTN_SPLITS_RT: the tests force each split count)
+  const XattnPlan plan = xattn_plan(T, R);
   return tiled_check(d, R, D, prec, out_dev, [&](_Float16* tiled) {
     return launch_xattn(q_dev, wk_dev, wv_dev, wvp, bv_dev, weight_type, enc, n_clips, Tq, T, H, D, qt, part, tiled,
-                        ns, res, nullptr);
+                        ns, res, plan, nullptr);
   });
 }
 
@@ -71,7 +73,15 @@ int wa_xattn_chunk_resident(int chunk, int share) {
 
 wq4_status wa_xattn_plan(int T, int* splits, int* chunks_per_split) {
   if (T < 1 || !splits || !chunks_per_split) return fail(WQ4_EINVAL, "bad arguments");
-  const XattnPlan p = xattn_plan(1, T);
+  const XattnPlan p = xattn_plan(T, 1, 0, 0);
+  *splits = p.splits;
+  *chunks_per_split = p.ch;
+  return WQ4_OK;
+}
+
+wq4_status wa_xattn_plan_splits(int T, int rows, int free_cus, int* splits, int* chunks_per_split) {
+  if (T < 1 || rows < 1 || !splits || !chunks_per_split) return fail(WQ4_EINVAL, "bad arguments");
+  const XattnPlan p = xattn_plan(T, rows, free_cus, 0);
   *splits = p.splits;
   *chunks_per_split = p.ch;
   return WQ4_OK;

@@ -407,7 +407,7 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
                                        m->ns, st, a32));
     } else {
       WA_HIP(launch_xattn(g.qd, L.ck_raw, L.cv_raw, L.cv_p, L.cv_b, m->wtype, enc, B, Tq, T, H, D, g.xqt,
-                          g.xattn_part, g.atd_dec, m->ns, g.xres, st, a32));
+                          g.xattn_part, g.atd_dec, m->ns, g.xres, g.xplan, st, a32));
     }
     WA_TRY(resid_gemm(L.cout, L.cout_b, g.atd_dec, a32, L.ln3_w));
     // FFN
@@ -495,11 +495,12 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
 wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
   // everything the captured step bakes in: the clip range (self-KV and
   // encoder-plane offsets), the EOT mode and the trace buffers, the range
-  // tier, the planes' cache residency (a group that decoded alone and then
+  // tier, the cross-attention's frame split (its splits fix the plan of a T)
+  // and the planes' cache residency (a group that decoded alone and then
   // decodes in a pair recaptures); one explicit field per mixed-radix digit
   const int64_t key =
-      (((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
-        (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * (kXattnResDen + 1) + g.xres.q;
+      ((((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
+         (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * 16 + g.xplan.splits) * (kXattnResDen + 1) + g.xres.q;
   if (g.graph && g.graph_key == key) return WQ4_OK;
   // the other layout's graph is kept: a call with an odd batch count goes
   // from pairs to its lone last batch and the next call back again

@@ -55,7 +55,13 @@ struct XattnPlan {
   int splits;  // frame ranges per query row (workgroups per row)
   int ch;      // 16-frame sub-chunks per range
 };
-XattnPlan xattn_plan(int R, int T);
+// The frame split of a decode (wa_xattn.hip): rows = the rows of the largest
+// concurrently decoding group, free_cus = the CUs the decode has while a
+// CU-masked stream runs beside it (<= 0: nothing beside it, no bound).
+// force_splits < 0: the product's rule (WA_XATTN_SPLITS_RT overrides it, A/B
+// runs and tests only), 0: the rule alone, > 0: that many splits (normalised).
+XattnPlan xattn_plan(int T, int rows = 1, int free_cus = 0, int force_splits = -1);
+// sized for every plan of up to the maximum (8) splits
 size_t xattn_part_floats(int R, int H, int D, int T);
 // Q4_0 Wv repacked once at model load into the cross-attention
 // projection's lane order (same bytes; wv_pack_words u32 words).
@@ -80,9 +86,11 @@ constexpr bool xattn_chunk_resident(int chunk, int q) { return ((chunk * q) & (k
 // product's rule, else a budget in MB (10^6 bytes) that replaces it.
 XattnResidency xattn_residency(int live_clips, int T, int ns, int D, double budget_mb = -1.0);
 // wvp: the launch_wv_pack words of wv (Q4 weights; ignored for f16 weights).
+// plan: an xattn_plan of T (no empty split, at most the maximum splits).
 hipError_t launch_xattn(const float* q, const uint8_t* wk, const uint8_t* wv, const uint32_t* wvp, const float* bv,
                         int wtype, const _Float16* enc, int B, int Tq, int T, int H, int D, _Float16* qt, float* part,
-                        _Float16* tiled, int ns, XattnResidency res, hipStream_t st, float* out32 = nullptr);
+                        _Float16* tiled, int ns, XattnResidency res, XattnPlan plan, hipStream_t st,
+                        float* out32 = nullptr);
 // A-tiled operand [R][K] (hi + lo) -> f32 rows (diagnostics).
 hipError_t launch_untile(const _Float16* tiled, int R, int K, int ns, float* out, hipStream_t st);
 // f32 rows [rows][D] -> [rows][ns][D] f16 planes (hi | lo) for launch_xattn.

@@ -116,6 +116,9 @@ struct DecGroup {
   // of (run_decode: from the clips of every group that decodes beside it);
   // baked into the captured step graph
   XattnResidency xres;
+  // the cross-attention's frame split for that decode (run_decode: one plan
+  // for all its groups, prompt and steps); baked into the step graph too
+  XattnPlan xplan{0, 0};
   float *xd, *qkvd, *qd, *hid, *logits;
   _Float16 *atd_dec, *atf_dec;
   int *prompt_tok, *next_tok, *tokens, *ntok, *done;
@@ -133,7 +136,7 @@ struct DecGroup {
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace, plane residency) the graph was captured for
+  int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
   hipGraphExec_t graph_alt = nullptr;  // the graph `graph` replaced last (ensure_graph)
   int64_t graph_alt_key = -1;
 };
@@ -187,6 +190,7 @@ struct wa_model {
   // layers that part covers (adapted per batch) and the last call's stats
   hipStream_t enc_stream = nullptr;
   int enc_cus = 0;
+  int dev_cus = 0;  // the device's CUs (run_decode)
   int overlap_k = -1;
   int overlap_b = 0, overlap_eot = -1;  // the batch shape overlap_k was adapted to
   float pipe[4] = {0, 0, 0, 0};

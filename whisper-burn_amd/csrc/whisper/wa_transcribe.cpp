@@ -14,9 +14,24 @@ namespace {
 // Fill measured at 32 clips (scripts/r05ad.sh): RTF 959 at 0.92, 966 at 0.98
 // / 1.0 / 1.02, 948 at 1.04 (the masked part then outlasts the decode);
 // 0.98 keeps ~30 ms of slack.
+// The masked CUs and the cross-attention's frame split are one decision
+// (xattn_plan, run_decode): swept together on the paired bench
+// (profiles/split_sweep.json), 32 CUs won -- RTF 1280 with 6 splits beside 32
+// CUs against 1273 beside 64, and 1260 / 1255 beside 48 / 64 with the rule's
+// 6 splits on all but the last pair.
 constexpr int kEncOverlapCUs = 32;
 constexpr int kEncOverlapLayers0 = 16;
 constexpr double kEncOverlapFill = 0.98;
+// CUs an xattn_main launch leaves to the other decode groups of its unit.
+// The main holds every CU it lands on for the whole launch, so a main on all
+// the CUs the decode has stalls the other group's chain of small GEMMs for
+// its length; the main itself is HBM-bound and as fast on fewer CUs.  Paired
+// bench, 32-row groups (profiles/split_gate.json, split_sweep.json,
+// split_bench_before.json): decode per batch with nothing beside it 626 /
+// 608 / 590 ms at 8 / 7 / 6 splits (0 / 32 / 64 CUs left), beside the 32-CU
+// masked stream 691 / 653 / 631 / 632 / 632 ms at 8 / 7 / 6 / 5 / 4 (none /
+// none / 32 / 64 / 96 left).
+constexpr int kXattnPeerCUs = 64;
 
 // HIP events destroyed with the set.
 struct EventSet {
@@ -60,18 +75,27 @@ int unit_groups(int B, bool pair) { return pair ? 2 : decode_groups(B); }
 // Prompt + greedy loop (whisper.rs:60-125) of every decode group of a batch
 // of B clips -- or, `pair`, of two batches of B clips, group i decoding the
 // batch in lane i -- each group's stream first waiting on `ready` (the
-// encoder planes).  Records gprompt[i] after group i's prompt and gdone[i]
-// after its last step, gsteps[i] = the steps it ran; the host blocks only for
-// the lagged EOT polls (eot_stop).
-wq4_status run_decode(wa_model* m, int B, bool pair, int lang_token, int max_tokens, int eot_stop, hipEvent_t ready,
-                      const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps) {
+// encoder planes).  masked_cus: the CUs of the masked stream that runs beside
+// this decode (0: nothing does).  Records gprompt[i] after group i's prompt
+// and gdone[i] after its last step, gsteps[i] = the steps it ran; the host
+// blocks only for the lagged EOT polls (eot_stop).
+wq4_status run_decode(wa_model* m, int B, bool pair, int masked_cus, int lang_token, int max_tokens, int eot_stop,
+                      hipEvent_t ready, const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps) {
   const int G = unit_groups(B, pair);
   // the groups decode concurrently: the planes of all their clips are live
   // (both lanes of a pair), which decides the share each keeps cached
   const XattnResidency xres = xattn_residency(pair ? 2 * B : B, m->cfg.n_audio_ctx, m->ns, m->cfg.n_audio_state);
+  // one frame split for the unit: its largest group's rows on the CUs a main
+  // has -- the device's less the masked stream's and, when other groups decode
+  // beside it, what it leaves to them
+  if (m->dev_cus <= 0) WA_HIP(hipDeviceGetAttribute(&m->dev_cus, hipDeviceAttributeMultiprocessorCount, m->device));
+  const int rows = pair ? B : (B + G - 1) / G;
+  const int free_cus = std::max(1, m->dev_cus - masked_cus - (G > 1 ? kXattnPeerCUs : 0));
+  const XattnPlan xplan = xattn_plan(m->cfg.n_audio_ctx, rows, free_cus);
   for (int i = 0; i < G; ++i) {
     DecGroup& g = m->groups[i];
     g.xres = xres;
+    g.xplan = xplan;
     g.lane = pair ? i : 0;
     g.b0 = pair ? 0 : (int)((int64_t)B * i / G);
     g.nb = pair ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
@@ -180,7 +204,7 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
   // decode groups: contiguous clip ranges on their own streams, started
   // after the encoder-planes pass, joined back into `st` at the end
   int gsteps[kMaxGroups] = {};
-  WA_TRY(run_decode(m, B, false, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, gsteps));
+  WA_TRY(run_decode(m, B, false, 0, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, gsteps));
   const int steps = *std::max_element(gsteps, gsteps + G);  // the last group to stop
   std::vector<int32_t> tok((size_t)B * kMaxTokens), nt(B);
   int flag = 0;
@@ -234,8 +258,14 @@ wq4_status ensure_enc_stream(wa_model* m) {
 // decode (it reads only the planes, rewritten after the decode it serves),
 // so nothing is double-buffered.  k adapts per batch to the last decode's
 // length over the masked stream's measured time per layer.  Every kernel
-// computes what it computes in wa_transcribe: the same tokens.  flags[i] =
-// batch i's range flag (the caller re-runs flagged batches).
+// computes what it computes in wa_transcribe, with one exception: a unit
+// sizes the cross-attention's frame split to the CUs the masked stream and
+// its other group leave a launch (run_decode, xattn_plan: a pair of 32-row
+// groups gets 5 ranges beside the stream and 6 alone, where the sequential
+// call's 16-row groups get 8), so a pipelined unit may use a different split
+// than the sequential call -- the same tokens, the partials merged in a
+// different grouping.  flags[i] = batch i's range flag (the caller re-runs
+// flagged batches).
 //
 // Batches of 16 .. 32 clips decode in pairs (see kPairMinClips): the decode
 // step is a chain of dependent launches whose cost barely grows with the
@@ -366,7 +396,9 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
       WA_TRY(encoder_layers(m, B, 0, u.k, es));
       WA_HIP(hipEventRecord(u.mend, es));
     }
-    WA_TRY(run_decode(m, B, pair, lang_token, max_tokens, eot_stop, u.ready, u.gprompt, u.gdone, u.gsteps));
+    // the masked part above takes its CUs from this decode; the last unit has them all
+    WA_TRY(run_decode(m, B, pair, i + 1 < NU ? m->enc_cus : 0, lang_token, max_tokens, eot_stop, u.ready, u.gprompt,
+                      u.gdone, u.gsteps));
     int32_t* hb = host + (size_t)u.first * per;
     WA_TRY(collect_batch(m, B, pair, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
                          per));

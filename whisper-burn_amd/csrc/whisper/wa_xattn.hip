@@ -60,7 +60,9 @@ constexpr float kZnScale = 32.0f, kWvScale = 4096.0f, kOutInv = 1.0f / (32.0f * 
 #ifndef WA_XATTN_SPLITS  // compile-time only: tuning builds (A/B: scripts/gpu.sh libs)
 #define WA_XATTN_SPLITS 8
 #endif
-// Frame ranges per query row.  Measured: 8 beat 4, 6, 12 and 16 in round 1;
+// Frame ranges per query row: the most a plan may have (xattn_plan picks the
+// count of a decode at run time) and xattn_out_kernel's compile-time maximum.
+// Measured: 8 beat 4, 6, 12 and 16 in round 1;
 // in round 2's model (two concurrent decode groups of 16 clips) 12 and 16 ran
 // the isolated 16-clip launch faster (50.5 us vs 55.7 at 12) but the decode
 // slower (926 / 1073 ms vs 873): more workgroups crowd out the other group.
@@ -1148,13 +1150,34 @@ void launch_out(int R, int H, const float* z, const float* ml, int D, int S, con
 
 }  // namespace
 
-// The frame split depends on T only -- never on the number of query rows --
-// so every row's arithmetic (and its tokens) is independent of the batch.
-// 8 ranges of 12 sub-chunks for T = 1500: 256 workgroups at 32 rows.
-XattnPlan xattn_plan(int R, int T) {
-  (void)R;
+// The frame split of a decode unit, decided once per run_decode for all its
+// groups and lanes, prompt and steps alike.  A row's arithmetic depends on T
+// and on this plan only -- never on the number of rows a launch batches it
+// with: under one plan a row's bits are those of the row alone.  The plan
+// itself is the largest S <= kXattnSplits with S * rows <= free_cus (at least
+// 1), normalised so that no split is empty: xattn_main holds a CU to itself
+// (480 of a SIMD's 512 registers, 129 KB of LDS) and all its workgroups last
+// the whole launch, so whatever else wants a CU the launch covers -- the
+// masked encoder stream, the other decode group's chain of small kernels --
+// waits for the whole launch or makes part of it wait a second round, while
+// the main, HBM-bound at 32 rows, is as fast on fewer CUs (DESIGN.md section
+// 10).  free_cus is what the caller leaves the main (run_decode); <= 0 puts
+// no bound.  Whenever 8 rows-wide splits fit the plan is 8 ranges -- 8 x 12
+// sub-chunks for T = 1500 -- which is every decode of groups of up to 16
+// rows; a pair of 32-row groups gets 6 x 16 alone and 5 x 19 beside the
+// 32-CU masked stream.  Two plans of the same T give the same tokens through
+// partials merged in a different grouping.  WA_XATTN_SPLITS_RT (A/B runs and
+// tests only) replaces S.
+XattnPlan xattn_plan(int T, int rows, int free_cus, int force_splits) {
   const int nchunk = (T + kTc - 1) / kTc;
-  const int S = std::max(1, std::min(kXattnSplits, nchunk));
+  int S = kXattnSplits;
+  if (free_cus > 0) S = std::min(S, free_cus / std::max(1, rows));
+  if (force_splits < 0) {
+    if (const char* e = getenv("WA_XATTN_SPLITS_RT")) S = atoi(e);
+  } else if (force_splits > 0) {
+    S = force_splits;
+  }
+  S = std::max(1, std::min({S, kXattnSplits, nchunk}));
   XattnPlan p;
   p.ch = (nchunk + S - 1) / S;
   p.splits = (nchunk + p.ch - 1) / p.ch;
@@ -1195,13 +1218,17 @@ XattnResidency xattn_residency(int live_clips, int T, int ns, int D, double budg
 }
 
 size_t xattn_part_floats(int R, int H, int D, int T) {
-  const XattnPlan p = xattn_plan(R, T);
-  size_t n = (size_t)R * p.splits * H * ((size_t)D + 2) + (size_t)R * H * D;
-  if (R <= kSmallRowsMax) {  // split-phase scratch: the scores (+ 16-B alignment)
-    const size_t ng = (size_t)p.splits * p.ch;
-    n = (n + 3) / 4 * 4 + (size_t)R * ng * 32 * 16 + 4;
+  size_t most = 0;
+  for (int S = 1; S <= kXattnSplits; ++S) {  // every plan a launch may be given
+    const XattnPlan p = xattn_plan(T, 1, 0, S);
+    size_t n = (size_t)R * p.splits * H * ((size_t)D + 2) + (size_t)R * H * D;
+    if (R <= kSmallRowsMax) {  // split-phase scratch: the scores (+ 16-B alignment)
+      const size_t ng = (size_t)p.splits * p.ch;
+      n = (n + 3) / 4 * 4 + (size_t)R * ng * 32 * 16 + 4;
+    }
+    most = std::max(most, n);
   }
-  return n;
+  return most;
 }
 
 hipError_t launch_untile(const _Float16* tiled, int R, int K, int ns, float* out, hipStream_t st) {
@@ -1234,13 +1261,17 @@ hipError_t launch_wv_pack(const uint8_t* wv, int H, int D, uint32_t* out, hipStr
 
 hipError_t launch_xattn(const float* q, const uint8_t* wk, const uint8_t* wv, const uint32_t* wvp, const float* bv,
                         int wtype, const _Float16* enc, int B, int Tq, int T, int H, int D, _Float16* qt, float* part,
-                        _Float16* tiled, int ns, XattnResidency res, hipStream_t st, float* out32) {
+                        _Float16* tiled, int ns, XattnResidency res, XattnPlan p, hipStream_t st, float* out32) {
   const int R = B * Tq;
   const int HT = (H + 15) / 16, HP = HT * 16;
   if (D != H * 64 || D % 128 != 0 || D > kMaxD || H > 20 || !q) return hipErrorInvalidValue;
   if (res.q < 0 || res.q > kXattnResDen) return hipErrorInvalidValue;
   if (wtype == kWtQ4 && !wvp) return hipErrorInvalidValue;  // Q4: the load-time packed Wv (launch_wv_pack)
-  const XattnPlan p = xattn_plan(R, T);
+  // a plan of this T: within what `part` is sized for, every split non-empty
+  const int nchunk = (T + kTc - 1) / kTc;
+  if (p.splits < 1 || p.splits > kXattnSplits || p.ch < 1 || (p.splits - 1) * p.ch >= nchunk ||
+      p.splits * p.ch < nchunk)
+    return hipErrorInvalidValue;
   float* z = part;
   float* ml = part + (size_t)R * p.splits * H * D;
   // qt = Wk^T q / 8

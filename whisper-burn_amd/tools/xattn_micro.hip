@@ -71,7 +71,7 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&a));
   CK(hipEventCreate(&b));
   for (int R : rows) {
-    const wa::XattnPlan p = wa::xattn_plan(R, T);
+    const wa::XattnPlan p = wa::xattn_plan(T, R);  // WA_XATTN_SPLITS_RT picks another split
     float* z = part;
     float* ml = part + (size_t)R * p.splits * H * D;
     auto time_it = [&](auto&& launch) -> float {
@@ -92,14 +92,14 @@ int main(int argc, char** argv) {
                          q, R, D, wk, HP, qt);
     });
     const float t_out = time_it([&] {
-      wa::launch_out<2, wa::kWtQ4>(R, H, z, ml, D, p.splits, wv, wvp, bv, tiled, 0);
+      wa::launch_out<2, wa::kWtQ4>(R, H, z, ml, D, p.splits, wv, wvp, bv, tiled, nullptr, 0);
     });
     const float t_out4 = time_it([&] {
-      wa::launch_out<2, wa::kWtQ4>(R, H, z, ml, D, p.splits, wv, wvp, bv, tiled, 0, true);
+      wa::launch_out<2, wa::kWtQ4>(R, H, z, ml, D, p.splits, wv, wvp, bv, tiled, nullptr, 0, true);
     });
     printf("{\"rows\": %d, \"out_split4_us\": %.2f}\n", R, t_out4);
     const float t_all = time_it([&] {
-      wa::launch_xattn(q, wk, wv, wvp, bv, wa::kWtQ4, enc, R, 1, T, H, D, qt, part, tiled, NS, wa::XattnResidency{}, 0);
+      wa::launch_xattn(q, wk, wv, wvp, bv, wa::kWtQ4, enc, R, 1, T, H, D, qt, part, tiled, NS, wa::XattnResidency{}, p, 0);
     });
     float t_sc = 0.0f, t_z = 0.0f;
     if (R <= wa::kSmallRowsMax) {  // the split phases one by one

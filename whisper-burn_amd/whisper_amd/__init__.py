@@ -80,6 +80,8 @@ def lib() -> ctypes.CDLL:
         L.wa_xattn_chunk_resident.restype = c_int
         L.wa_xattn_plan.argtypes = [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
         L.wa_xattn_plan.restype = c_int
+        L.wa_xattn_plan_splits.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        L.wa_xattn_plan_splits.restype = c_int
         L.wa_decode_graph_key.argtypes = [vp, c_int]
         L.wa_decode_graph_key.restype = ctypes.c_longlong
         L.wa_xattn_kv_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
@@ -195,6 +197,16 @@ def xattn_plan(T: int) -> tuple[int, int]:
     """(splits, sub-chunks per split) of the cross-attention's frame split for T frames."""
     s, c = ctypes.c_int(), ctypes.c_int()
     check(lib().wa_xattn_plan(T, ctypes.byref(s), ctypes.byref(c)))
+    return s.value, c.value
+
+
+def xattn_plan_splits(T: int, rows: int, free_cus: int) -> tuple[int, int]:
+    """(splits, sub-chunks per split) of a decode whose largest group has `rows`
+    rows and whose cross-attention launches may take free_cus CUs (<= 0: no
+    bound): the host rule (wa_xattn_plan_splits), without the
+    WA_XATTN_SPLITS_RT override."""
+    s, c = ctypes.c_int(), ctypes.c_int()
+    check(lib().wa_xattn_plan_splits(T, rows, free_cus, ctypes.byref(s), ctypes.byref(c)))
     return s.value, c.value
 
 
