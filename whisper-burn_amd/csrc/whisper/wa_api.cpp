@@ -210,7 +210,7 @@ wq4_status wa_probe_kernels(wa_model* m, int n_clips, int iters, double* out, in
   const int B = n_clips, D = c.n_text_state, T = c.n_audio_ctx, H = c.n_text_head;
   DecLayer& L = m->dec[0];
   DecGroup g = m->groups[0];  // group 0's buffers, a clip range of its own
-  const _Float16* enc = m->enc_planes;
+  const _Float16* enc = m->lanes[0].planes;
   hipEvent_t a, b;
   WA_HIP(hipEventCreate(&a));
   WA_HIP(hipEventCreate(&b));

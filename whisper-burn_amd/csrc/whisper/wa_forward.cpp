@@ -109,11 +109,12 @@ wq4_status alloc_activations(wa_model* m) {
   m->qkv = f32(renc * 3 * D);
   m->at_d = tiled(renc, D);
   m->at_f = tiled(renc, F);
-  m->enc_planes = d.alloc<_Float16>((size_t)renc * m->ns * D);
+  Lane& lane0 = m->lanes[0];  // the further lanes: ensure_lanes
+  lane0.planes = d.alloc<_Float16>((size_t)renc * m->ns * D);
   m->bytes += (size_t)renc * m->ns * D * 2;
-  for (auto& L : m->dec) {
-    L.cache_k = f32((int64_t)B * c.n_text_ctx * Dt);
-    L.cache_v = f32((int64_t)B * c.n_text_ctx * Dt);
+  for (size_t li = 0; li < m->dec.size(); ++li) {
+    lane0.cache_k.push_back(f32((int64_t)B * c.n_text_ctx * Dt));
+    lane0.cache_v.push_back(f32((int64_t)B * c.n_text_ctx * Dt));
   }  // the cross K / V caches: on the first transcribe that reads them (cross_kv_forward)
   // f16-pair tied embedding for the decode step's fused logits + pick,
   // fragment-tiled (1 KiB contiguous per load instruction)
@@ -171,12 +172,12 @@ wq4_status alloc_activations(wa_model* m) {
     WA_HIP(hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking));
   }
   m->range_flag = d.alloc<int>(1);
-  for (void* p : {(void*)m->h1, (void*)m->x, (void*)m->qkv, (void*)m->at_d, (void*)m->at_f, (void*)m->enc_planes,
+  for (void* p : {(void*)m->h1, (void*)m->x, (void*)m->qkv, (void*)m->at_d, (void*)m->at_f, (void*)lane0.planes,
                   (void*)m->range_flag})
     if (!p) return fail(WQ4_ENOMEM, "activation allocation failed");
   WA_HIP(hipMemset(m->range_flag, 0, sizeof(int)));
-  for (auto& L : m->dec)
-    if (!L.cache_k || !L.cache_v) return fail(WQ4_ENOMEM, "KV cache allocation failed");
+  for (size_t li = 0; li < m->dec.size(); ++li)
+    if (!lane0.cache_k[li] || !lane0.cache_v[li]) return fail(WQ4_ENOMEM, "KV cache allocation failed");
   // zero the A-tiled buffers once: padded rows stay finite forever
   WA_HIP(hipMemset(m->at_d, 0, wq4_atiled_bytes(renc, D, m->prec)));
   WA_HIP(hipMemset(m->at_f, 0, wq4_atiled_bytes(renc, F, m->prec)));
@@ -288,12 +289,10 @@ wq4_status encoder_forward(wa_model* m, const float* mel, int B, hipStream_t st,
 wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches, int lane) {
   const Config& c = m->cfg;
   const int64_t rows = (int64_t)B * c.n_audio_ctx;
-  if (lane == 1) {  // a paired batch's planes (more clips than the caches serve: no caches)
-    WA_HIP(launch_enc_planes(m->enc_f32, rows, c.n_audio_state, m->ns, m->enc_planes2, st));
-    return WQ4_OK;
-  }
+  WA_HIP(launch_enc_planes(m->enc_f32, rows, c.n_audio_state, m->ns, m->lanes[lane].planes, st));
+  // a further lane's batch is one of a unit (more clips than the caches serve: no caches)
+  if (lane > 0) return WQ4_OK;
   m->kv_batch = B;
-  WA_HIP(launch_enc_planes(m->enc_f32, rows, c.n_audio_state, m->ns, m->enc_planes, st));
   m->kv_n = caches && B <= m->kv_small ? B : 0;
   if (m->kv_n > 0 && !m->kv_alloc_ok) {
     // all layers or none: a partial failure frees what it got, so the next
@@ -346,7 +345,8 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
   const int B = g.nb;
   const int64_t rows = (int64_t)B * Tq;
   const size_t self_ofs = (size_t)g.b0 * H * c.n_text_ctx * 64;
-  const _Float16* enc = (g.lane ? m->enc_planes2 : m->enc_planes) + (size_t)g.b0 * T * m->ns * c.n_audio_state;
+  const Lane& lane = m->lanes[g.lane];
+  const _Float16* enc = lane.planes + (size_t)g.b0 * T * m->ns * c.n_audio_state;
   // Decode steps fold every decoder LayerNorm into the GEMMs around it
   // (wq4_gemm_tiled_lnfold): the residual GEMM producing x also writes
   // tiled(x * gamma) and tile statistics, the GEMM reading LN(x) corrects
@@ -395,9 +395,8 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
     DecLayer& L = m->dec[li];
     // self-attention
     WA_TRY(ln_gemm(L.qkv, L.qkv_b, L.qkv_wg, L.qkv_b2, L.ln1_w, L.ln1_b, g.qkvd, nullptr, 0u));
-    WA_HIP(launch_decoder_self_attention(g.qkvd, (g.lane ? L.cache_k2 : L.cache_k) + self_ofs,
-                                         (g.lane ? L.cache_v2 : L.cache_v) + self_ofs, B, Tq, H, c.n_text_ctx, state,
-                                         kv0, g.atd_dec, m->ns, st, a32));
+    WA_HIP(launch_decoder_self_attention(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, Tq, H,
+                                         c.n_text_ctx, state, kv0, g.atd_dec, m->ns, st, a32));
     WA_TRY(resid_gemm(L.out, L.out_b, g.atd_dec, a32, L.ln2_w));
     // cross-attention
     WA_TRY(ln_gemm(L.cq, L.cq_b, L.cq_wg, L.cq_b2, L.ln2_w, L.ln2_b, g.qd, nullptr, 0u));
@@ -502,14 +501,28 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
       ((((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
          (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * 16 + g.xplan.splits) * (kXattnResDen + 1) + g.xres.q;
   if (g.graph && g.graph_key == key) return WQ4_OK;
-  // the other layout's graph is kept: a call with an odd batch count goes
-  // from pairs to its lone last batch and the next call back again
-  std::swap(g.graph, g.graph_alt);
-  std::swap(g.graph_key, g.graph_alt_key);
-  if (g.graph && g.graph_key == key) return WQ4_OK;
-  if (g.graph) {
-    (void)hipGraphExecDestroy(g.graph);
+  // the other layouts' graphs are kept: a call goes from units of three to
+  // pairs or a lone last batch, beside the masked stream and without it, and
+  // the next call back again
+  for (DecGroup::KeptGraph& k : g.kept)
+    if (k.exec && k.key == key) {
+      std::swap(g.graph, k.exec);
+      std::swap(g.graph_key, k.key);
+      return WQ4_OK;
+    }
+  if (g.graph) {  // park it: in a free slot, else in place of the one parked longest ago
+    DecGroup::KeptGraph* slot = nullptr;
+    for (DecGroup::KeptGraph& k : g.kept)
+      if (!k.exec && !slot) slot = &k;
+    if (!slot) {
+      slot = &g.kept[g.kept_next];
+      g.kept_next = (g.kept_next + 1) % kKeptGraphs;
+      (void)hipGraphExecDestroy(slot->exec);
+    }
+    slot->exec = g.graph;
+    slot->key = g.graph_key;
     g.graph = nullptr;
+    g.graph_key = -1;
   }
   WA_WQ4(wq4_prepare_stream(m->device, g.st));  // split-K workspace exists before capture
   hipGraph_t gr;
@@ -572,35 +585,35 @@ wq4_status ensure_ffn_ws(wa_model* m) {
   return WQ4_OK;
 }
 
-// The second lane (wa_model::enc_planes2, DecLayer::cache_k2 / cache_v2),
-// sized like the first; false (and nothing held) when the device has no room
-// for it: the caller then decodes unpaired.
-bool ensure_pair_lane(wa_model* m) {
-  if (m->enc_planes2) return true;
+// Lanes [0, want) of the per-clip decode state (wa_model::lanes), each sized
+// like lane 0.  Returns the lanes the model has afterwards, at most `want`:
+// a lane the device has no room for is not held in part, and the caller
+// decodes narrower units (two lanes: pairs; one: every batch on its own).
+int ensure_lanes(wa_model* m, int want) {
+  want = std::min(want, kMaxLanes);
   const Config& c = m->cfg;
   const size_t np = (size_t)m->bmax * c.n_audio_ctx * m->ns * c.n_audio_state;
   const size_t nc = (size_t)m->bmax * c.n_text_ctx * c.n_text_state;
-  _Float16* planes = m->dev.alloc<_Float16>(np);
-  bool ok = planes != nullptr;
-  for (DecLayer& L : m->dec) {
-    if (!ok) break;
-    L.cache_k2 = m->dev.alloc<float>(nc);
-    L.cache_v2 = m->dev.alloc<float>(nc);
-    ok = L.cache_k2 && L.cache_v2;
-  }
-  if (!ok) {
-    (void)hipGetLastError();  // the failed hipMalloc is handled here
-    m->dev.release(planes);
-    for (DecLayer& L : m->dec) {
-      m->dev.release(L.cache_k2);
-      m->dev.release(L.cache_v2);
-      L.cache_k2 = L.cache_v2 = nullptr;
+  while (m->n_lanes < want) {
+    Lane lane;
+    lane.planes = m->dev.alloc<_Float16>(np);
+    bool ok = lane.planes != nullptr;
+    for (size_t li = 0; ok && li < m->dec.size(); ++li) {
+      lane.cache_k.push_back(m->dev.alloc<float>(nc));
+      lane.cache_v.push_back(m->dev.alloc<float>(nc));
+      ok = lane.cache_k.back() && lane.cache_v.back();
     }
-    return false;
+    if (!ok) {
+      (void)hipGetLastError();  // the failed hipMalloc is handled here
+      m->dev.release(lane.planes);
+      for (float* p : lane.cache_k) m->dev.release(p);
+      for (float* p : lane.cache_v) m->dev.release(p);
+      break;
+    }
+    m->lanes[m->n_lanes++] = std::move(lane);
+    m->bytes += np * 2 + nc * 8 * m->dec.size();
   }
-  m->enc_planes2 = planes;
-  m->bytes += np * 2 + nc * 8 * m->dec.size();
-  return true;
+  return std::min(m->n_lanes, want);
 }
 
 // Number of decode groups for a batch (WA_DECODE_GROUPS overrides).

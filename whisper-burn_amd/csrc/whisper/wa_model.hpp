@@ -89,9 +89,7 @@ struct DecLayer {
   // f16), read by the K/V-cache-free cross-attention (wa_xattn.hip)
   uint8_t *ck_raw = nullptr, *cv_raw = nullptr;
   uint32_t* cv_p = nullptr;  // Q4_0: cv_raw in the projection's lane order (wa::launch_wv_pack)
-  float *cache_k, *cache_v;
-  // the second lane's self-attention caches (wa_model::ensure_pair_lane)
-  float *cache_k2 = nullptr, *cache_v2 = nullptr;
+  // (the self-attention caches are per lane: wa::Lane)
   // few-clip decode groups (wa_model::kv_clips): the reference's per-layer
   // cross K / V caches, head-major [clip][head][T][64] f32, written by the
   // head-major GEMMs of ck / cv over the encoder output (cross_kv_forward)
@@ -99,15 +97,28 @@ struct DecLayer {
   float *xk = nullptr, *xv = nullptr;
 };
 
+// One lane of per-clip decode state, bmax clips: the encoder output as f16
+// planes [clip][T][ns][D] (the cross-attention's only per-clip state, no
+// per-layer K/V caches) and every decoder layer's self-attention caches
+// [clip][ctx][D] f32.  Lane 0 always exists; a wa_transcribe_batches that
+// decodes n batches at once, one decode group per batch, puts batch j in lane
+// j (ensure_lanes: allocated by the first call that needs them, all or
+// nothing per lane, never released).
+constexpr int kMaxLanes = 3;
+struct Lane {
+  _Float16* planes = nullptr;
+  std::vector<float*> cache_k, cache_v;  // per decoder layer
+};
+
 // One decode group: a contiguous range of clips [b0, b0 + nb) of one lane
-// (wa_model::enc_planes / enc_planes2 and the layers' self-attention caches
-// of that lane) decoded on its own stream with its own activations, DecodeState and step graph.  The
+// (wa_model::lanes) decoded on its own stream with its own activations, DecodeState and step graph.  The
 // decode step is a chain of ~350 small dependent kernels (latency-bound);
 // groups on separate streams overlap one another's launch gaps and let the
 // HBM-bound cross-attention of one group run beside the latency-bound GEMMs
 // of another.  Per-clip results do not depend on the grouping (every
 // kernel's per-row arithmetic is independent of the batch).
 constexpr int kMaxGroups = 4;
+constexpr int kKeptGraphs = 4;
 struct DecGroup {
   hipStream_t st = nullptr;
   int b0 = 0, nb = 0;
@@ -137,8 +148,15 @@ struct DecGroup {
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
   int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
-  hipGraphExec_t graph_alt = nullptr;  // the graph `graph` replaced last (ensure_graph)
-  int64_t graph_alt_key = -1;
+  // graphs of other layouts this group ran (ensure_graph): a call of units of
+  // three and two, with and without the masked stream beside them, goes
+  // through four keys per group and comes back to each
+  struct KeptGraph {
+    hipGraphExec_t exec = nullptr;
+    int64_t key = -1;
+  };
+  KeptGraph kept[kKeptGraphs];
+  int kept_next = 0;  // the slot the next parked graph replaces once all are taken
 };
 
 }  // namespace wa
@@ -160,21 +178,15 @@ struct wa_model {
   // encoder activations
   float *h1, *x, *qkv;
   _Float16 *at_d, *at_f;
-  // encoder output as f16 planes [clip][T][ns][D], the cross-attention's
-  // only per-clip state (no per-layer K/V caches)
-  _Float16* enc_planes = nullptr;
-  // Second lane of the per-clip decode state (the encoder planes here, the
-  // layers' cache_k2 / cache_v2), bmax clips like the first: a paired
-  // wa_transcribe_batches decodes two batches at once, one decode group per
-  // batch, group 1 on this lane.  Allocated by the first paired call
-  // (ensure_pair_lane); all or nothing.
-  _Float16* enc_planes2 = nullptr;
+  // per-clip decode state: lanes [0, n_lanes) are allocated (see wa::Lane)
+  wa::Lane lanes[wa::kMaxLanes];
+  int n_lanes = 1;
   const float* enc_f32 = nullptr;  // ln_post output of the last encoder pass
   // decode groups: the clips of a transcribe split over up to kMaxGroups
   // independent streams, each replaying its own step graph (see DecGroup)
   std::vector<wa::DecGroup> groups;
   int wtype = 0;     // linear weights: 0 Q4_0, 1 f16 (BASELINE config 5)
-  int kv_batch = 0;  // clips of the last encoder pass (enc_planes valid for [0, kv_batch))
+  int kv_batch = 0;  // clips of the last encoder pass (lane 0's planes valid for [0, kv_batch))
   // Cross K / V caches (capacity kv_clips clips) for transcribes of at most
   // kv_small clips -- their decode steps are launch-latency chains: one GEMV
   // launch over the caches replaces the cache-free cross-attention's four,
@@ -194,7 +206,8 @@ struct wa_model {
   int overlap_k = -1;
   int overlap_b = 0, overlap_eot = -1;  // the batch shape overlap_k was adapted to
   float pipe[4] = {0, 0, 0, 0};
-  int pipe_pairs = 0;  // batch pairs the last wa_transcribe_batches decoded together
+  // units of exactly two / of three batches the last wa_transcribe_batches decoded together
+  int pipe_pairs = 0, pipe_units3 = 0;
   // Activation-range guard.  Every internal producer writes MFMA operands as
   // f16 pairs of x * 2^4 (wq4_device.hpp split_act), finite for |x| < 4094;
   // beyond that the f16 half overflows and the clip's logits become inf /
@@ -259,7 +272,8 @@ struct wa_model {
     resolve_profile();
     for (auto& g : groups) {
       if (g.graph) (void)hipGraphExecDestroy(g.graph);
-      if (g.graph_alt) (void)hipGraphExecDestroy(g.graph_alt);
+      for (auto& k : g.kept)
+        if (k.exec) (void)hipGraphExecDestroy(k.exec);
       if (g.st) (void)hipStreamDestroy(g.st);
       if (g.host_ndone) (void)hipHostFree(g.host_ndone);
     }
@@ -302,7 +316,7 @@ wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);
 wq4_status encoder_post(wa_model* m, int B, hipStream_t st, float* enc_out_f32);
 wq4_status encoder_forward(wa_model* m, const float* mel, int B, hipStream_t st, float* enc_out_f32);
 wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches, int lane = 0);
-bool ensure_pair_lane(wa_model* m);
+int ensure_lanes(wa_model* m, int want);
 wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, const DecodeState* state, int pos0,
                            int kv0, hipStream_t st);
 wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st);

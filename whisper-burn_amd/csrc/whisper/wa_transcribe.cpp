@@ -59,7 +59,15 @@ struct EventSet {
 // three interleaved runs each (profiles/pair_overlap_ab.json): RTF 1146.6 /
 // 1146.2 / 1144.1 adapted (decode 721 ms, encoder exposed 106 ms per batch)
 // against 1138.0 / 1132.1 / 1134.8 with the conv stem only (673 / 161 ms).
+// Three at a time (the width below) from 17 clips on: there a group's
+// xattn_main is the HBM-bound 32-row form, and while it streams its planes
+// the two other groups walk their chains of small launches, so the planes of
+// a third batch fill what a pair leaves of the HBM time (DESIGN.md section
+// 10, profiles/lanes_gate.json).  Batches of exactly 16 clips keep the paired
+// schedule: their main is the 16-row latency form, which more groups only
+// multiply.
 constexpr int kPairMinClips = 16, kPairMaxClips = 32;
+constexpr int kTripleMinClips = 17;
 
 bool pair_enabled() {
   static const bool enabled = [] {
@@ -69,36 +77,64 @@ bool pair_enabled() {
   return enabled;
 }
 
-// Decode groups of one run_decode: a pair's two batches, or one batch's groups.
-int unit_groups(int B, bool pair) { return pair ? 2 : decode_groups(B); }
+// Most batches one unit decodes at once: WA_LANES = 1 .. kMaxLanes caps it (A/B runs).
+int lanes_cap() {
+  static const int cap = [] {
+    const char* e = getenv("WA_LANES");
+    return e ? std::max(1, std::min(kMaxLanes, atoi(e))) : kMaxLanes;
+  }();
+  return cap;
+}
+
+// Sizes of the units a call over NB batches decodes at up to `width` batches
+// at once: widest first, and no lone last batch where taking one batch fewer
+// leaves a unit of two (4 -> 2 + 2, 7 -> 3 + 2 + 2) -- a lone batch of 17 ..
+// 32 clips decodes in two groups of half its rows, the slowest form there is.
+std::vector<int> unit_sizes(int NB, int width) {
+  std::vector<int> sizes;
+  for (int rem = NB; rem > 0; rem -= sizes.back()) {
+    int n = std::min(width, rem);
+    if (rem - n == 1 && n > 2) --n;
+    sizes.push_back(n);
+  }
+  return sizes;
+}
+
+// Decode groups of one run_decode: one per batch of a unit of n > 1 batches, or one batch's groups.
+int unit_groups(int B, int n) { return n > 1 ? n : decode_groups(B); }
 
 // Prompt + greedy loop (whisper.rs:60-125) of every decode group of a batch
-// of B clips -- or, `pair`, of two batches of B clips, group i decoding the
-// batch in lane i -- each group's stream first waiting on `ready` (the
-// encoder planes).  masked_cus: the CUs of the masked stream that runs beside
-// this decode (0: nothing does).  Records gprompt[i] after group i's prompt
-// and gdone[i] after its last step, gsteps[i] = the steps it ran; the host
-// blocks only for the lagged EOT polls (eot_stop).
-wq4_status run_decode(wa_model* m, int B, bool pair, int masked_cus, int lang_token, int max_tokens, int eot_stop,
+// of B clips -- or, n > 1, of a unit of n batches of B clips, group i
+// decoding the batch in lane i -- each group's stream first waiting on
+// `ready` (the encoder planes).  masked_cus: the CUs of the masked stream
+// that runs beside this decode (0: nothing does).  Records gprompt[i] after
+// group i's prompt and gdone[i] after its last step, gsteps[i] = the steps it
+// ran; the host blocks only for the lagged EOT polls (eot_stop).
+// With three groups of 32 rows there is a main to run most of the time: one
+// group's xattn_main streams planes while the other two walk their chains on
+// the CUs it leaves them (kXattnPeerCUs), so HBM idles less than beside one
+// chain (measurements and the sweeps of kXattnPeerCUs and the residency
+// budget at three lanes: DESIGN.md section 10).
+wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token, int max_tokens, int eot_stop,
                       hipEvent_t ready, const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps) {
-  const int G = unit_groups(B, pair);
+  const int G = unit_groups(B, n);
   // the groups decode concurrently: the planes of all their clips are live
-  // (both lanes of a pair), which decides the share each keeps cached
-  const XattnResidency xres = xattn_residency(pair ? 2 * B : B, m->cfg.n_audio_ctx, m->ns, m->cfg.n_audio_state);
+  // (every lane of a unit), which decides the share each keeps cached
+  const XattnResidency xres = xattn_residency(n * B, m->cfg.n_audio_ctx, m->ns, m->cfg.n_audio_state);
   // one frame split for the unit: its largest group's rows on the CUs a main
   // has -- the device's less the masked stream's and, when other groups decode
   // beside it, what it leaves to them
   if (m->dev_cus <= 0) WA_HIP(hipDeviceGetAttribute(&m->dev_cus, hipDeviceAttributeMultiprocessorCount, m->device));
-  const int rows = pair ? B : (B + G - 1) / G;
+  const int rows = n > 1 ? B : (B + G - 1) / G;
   const int free_cus = std::max(1, m->dev_cus - masked_cus - (G > 1 ? kXattnPeerCUs : 0));
   const XattnPlan xplan = xattn_plan(m->cfg.n_audio_ctx, rows, free_cus);
   for (int i = 0; i < G; ++i) {
     DecGroup& g = m->groups[i];
     g.xres = xres;
     g.xplan = xplan;
-    g.lane = pair ? i : 0;
-    g.b0 = pair ? 0 : (int)((int64_t)B * i / G);
-    g.nb = pair ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
+    g.lane = n > 1 ? i : 0;
+    g.b0 = n > 1 ? 0 : (int)((int64_t)B * i / G);
+    g.nb = n > 1 ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
     WA_HIP(hipStreamWaitEvent(g.st, ready, 0));
     WA_TRY(prompt_group(m, g, lang_token, g.st));
     WA_HIP(hipEventRecord(gprompt[i], g.st));
@@ -150,11 +186,11 @@ wq4_status run_decode(wa_model* m, int B, bool pair, int masked_cus, int lang_to
 
 // `st` waits for every group of the run_decode, then copies the groups'
 // tokens / counts (kMaxTokens per clip) and the range flag to (pinned) host
-// memory: tok / nt / flag of the batch in lane 0; a pair's second batch has
-// its own lane_stride int32 further on in each.
-wq4_status collect_batch(wa_model* m, int B, bool pair, const hipEvent_t* gdone, hipStream_t st, int32_t* tok,
+// memory: tok / nt / flag of the batch in lane 0; the batch in lane j of a
+// unit of n has its own j * lane_stride int32 further on in each.
+wq4_status collect_batch(wa_model* m, int B, int n, const hipEvent_t* gdone, hipStream_t st, int32_t* tok,
                          int32_t* nt, int* flag, size_t lane_stride) {
-  const int G = unit_groups(B, pair);
+  const int G = unit_groups(B, n);
   for (int i = 0; i < G; ++i) WA_HIP(hipStreamWaitEvent(st, gdone[i], 0));
   for (int i = 0; i < G; ++i) {
     const DecGroup& g = m->groups[i];
@@ -163,8 +199,8 @@ wq4_status collect_batch(wa_model* m, int B, bool pair, const hipEvent_t* gdone,
                           hipMemcpyDeviceToHost, st));
     WA_HIP(hipMemcpyAsync(nt + ofs + g.b0, g.ntok, (size_t)g.nb * 4, hipMemcpyDeviceToHost, st));
   }
-  // one flag word, set by either lane: a flagged pair flags both its batches
-  for (int i = 0; i < (pair ? 2 : 1); ++i)
+  // one flag word, set by any lane: a flagged unit flags all its batches
+  for (int i = 0; i < n; ++i)
     WA_HIP(hipMemcpyAsync(flag + i * lane_stride, m->range_flag, sizeof(int), hipMemcpyDeviceToHost, st));
   return WQ4_OK;
 }
@@ -204,11 +240,11 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
   // decode groups: contiguous clip ranges on their own streams, started
   // after the encoder-planes pass, joined back into `st` at the end
   int gsteps[kMaxGroups] = {};
-  WA_TRY(run_decode(m, B, false, 0, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, gsteps));
+  WA_TRY(run_decode(m, B, 1, 0, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, gsteps));
   const int steps = *std::max_element(gsteps, gsteps + G);  // the last group to stop
   std::vector<int32_t> tok((size_t)B * kMaxTokens), nt(B);
   int flag = 0;
-  WA_TRY(collect_batch(m, B, false, gdone, st, tok.data(), nt.data(), &flag, 0));
+  WA_TRY(collect_batch(m, B, 1, gdone, st, tok.data(), nt.data(), &flag, 0));
   WA_HIP(hipEventRecord(e_end, st));
   WA_HIP(hipStreamSynchronize(st));
   *overflow = flag != 0;
@@ -280,16 +316,32 @@ wq4_status ensure_enc_stream(wa_model* m) {
 // serves both, in turn), and one `ready` event starts both groups.  An odd
 // last batch is a unit of its own on today's groups.  The same four streams
 // as unpaired; a batch's tokens are complete when its unit is.
+//
+// Batches of 17 .. 32 clips decode up to three at a time (kTripleMinClips,
+// WA_LANES): a unit of n batches is the same loop at n lanes -- group j
+// decodes batch first + j from lane j, the model stream runs the unit's
+// encoders one after another into their lanes (all but the first exposed),
+// the plane residency is sized to the n * B live clips and the frame split,
+// as for a pair, to the CUs the masked stream and the peer groups leave.  A
+// call is cut into units by unit_sizes: widest first, and two units of two
+// in place of a unit of three and a lone batch.  One more group stream.
 wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B, int lang_token, int max_tokens,
                                 int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags) {
   WA_TRY(ensure_enc_stream(m));
   hipStream_t st = m->own_stream, es = m->enc_stream;
   const int L = (int)m->enc.size();
   const size_t mel_stride = (size_t)B * m->cfg.n_mels * 2 * m->cfg.n_audio_ctx;
-  // pairs need the encoder-plane groups (not the few-clip K/V caches), the
-  // default two groups per batch and room for the second lane
-  const bool pairing = pair_enabled() && NB >= 2 && B >= kPairMinClips && B <= kPairMaxClips && B > m->kv_small &&
-                       decode_groups(B) == 2 && ensure_pair_lane(m);
+  // units of several batches need the encoder-plane groups (not the few-clip
+  // K/V caches), the default two groups per batch and room for their lanes:
+  // only the lanes the widest unit of this call uses are allocated, and a
+  // device without room for them gets the units it has lanes for
+  int width = 1;
+  if (pair_enabled() && B >= kPairMinClips && B <= kPairMaxClips && B > m->kv_small && decode_groups(B) == 2)
+    width = std::min(lanes_cap(), B >= kTripleMinClips ? kMaxLanes : 2);
+  std::vector<int> sizes = unit_sizes(NB, width);
+  const int widest = *std::max_element(sizes.begin(), sizes.end());
+  const int lanes = ensure_lanes(m, widest);
+  if (lanes < widest) sizes = unit_sizes(NB, lanes);
   // pinned result staging: per batch the groups' tokens, counts and range flag
   int32_t* host = nullptr;
   const size_t per = (size_t)B * kMaxTokens + B + 1;
@@ -315,16 +367,15 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
     hipEvent_t ready, mstart, mend, pstart, gprompt[kMaxGroups], gdone[kMaxGroups];
     int k = 0, gsteps[kMaxGroups] = {};
   };
-  std::vector<Unit> ut;
-  for (int i = 0; i < NB; i += ut.back().n) {
-    ut.emplace_back();
-    ut.back().first = i;
-    ut.back().n = pairing && NB - i >= 2 ? 2 : 1;
-  }
+  std::vector<Unit> ut(sizes.size());
   const int NU = (int)ut.size();
+  for (int i = 0, first = 0; i < NU; first += sizes[i++]) {
+    ut[i].first = first;
+    ut[i].n = sizes[i];
+  }
   for (Unit& u : ut) {
     for (hipEvent_t* e : {&u.ready, &u.mstart, &u.mend, &u.pstart}) WA_HIP(ev.make(e));
-    for (int i = 0; i < unit_groups(B, u.n == 2); ++i) {
+    for (int i = 0; i < unit_groups(B, u.n); ++i) {
       WA_HIP(ev.make(&u.gprompt[i]));
       WA_HIP(ev.make(&u.gdone[i]));
     }
@@ -364,13 +415,12 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
   int32_t steps_all = 0;
   for (int i = 0; i < NU; ++i) {
     Unit& u = ut[i];
-    const bool pair = u.n == 2;
     if (i >= 1) {
       // unit i - 1 is decoded (and unit i's masked part done) before unit
       // i's decode is enqueued: the GPU meanwhile runs unit i's remaining
       // encoder work; adapt k to the finished decode
       Unit& p = ut[i - 1];
-      const int PG = unit_groups(B, p.n == 2);
+      const int PG = unit_groups(B, p.n);
       for (int g = 0; g < PG; ++g) WA_HIP(hipEventSynchronize(p.gdone[g]));
       WA_HIP(hipEventSynchronize(p.mend));
       float td = 0.0f, tm = 0.0f;
@@ -397,10 +447,10 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
       WA_HIP(hipEventRecord(u.mend, es));
     }
     // the masked part above takes its CUs from this decode; the last unit has them all
-    WA_TRY(run_decode(m, B, pair, i + 1 < NU ? m->enc_cus : 0, lang_token, max_tokens, eot_stop, u.ready, u.gprompt,
+    WA_TRY(run_decode(m, B, u.n, i + 1 < NU ? m->enc_cus : 0, lang_token, max_tokens, eot_stop, u.ready, u.gprompt,
                       u.gdone, u.gsteps));
     int32_t* hb = host + (size_t)u.first * per;
-    WA_TRY(collect_batch(m, B, pair, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
+    WA_TRY(collect_batch(m, B, u.n, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
                          per));
     if (i + 1 < NU) {  // the rest of the next unit's encoder work at full width
       WA_HIP(hipStreamWaitEvent(st, u.mend, 0));
@@ -416,11 +466,14 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
                 n_tokens_out + (size_t)i * B);
     flags[i] = hb[(size_t)B * kMaxTokens + B];
   }
-  // per-unit phases, averaged over the batches below: a pair's exposed
-  // encoder, prompt and decode times count half for each of its batches
+  // per-unit phases, averaged over the batches below: the exposed encoder,
+  // prompt and decode times of a unit of n count 1 / n for each of its batches
+  int pairs = 0, units3 = 0;
   for (int i = 0; i < NU; ++i) {
     Unit& u = ut[i];
-    const int UG = unit_groups(B, u.n == 2);
+    const int UG = unit_groups(B, u.n);
+    pairs += u.n == 2;
+    units3 += u.n == 3;
     float t = 0.0f, tp = 0.0f, td = 0.0f;
     if (i == 0) {
       WA_HIP(hipEventElapsedTime(&t, e_enc0, u.ready));
@@ -441,8 +494,11 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
     }
     t_prompt += tp;
     t_decode += td - tp;
-    // steps of a batch: its group's in a pair, else the last group's to stop
-    steps_all += u.n == 2 ? u.gsteps[0] + u.gsteps[1] : *std::max_element(u.gsteps, u.gsteps + UG);
+    // steps of a batch: its group's in a unit of several, else the last group's to stop
+    if (u.n > 1)
+      for (int g = 0; g < u.n; ++g) steps_all += u.gsteps[g];
+    else
+      steps_all += *std::max_element(u.gsteps, u.gsteps + UG);
   }
   m->timings[0] = (float)(t_exposed / NB);
   m->timings[1] = 0.0f;
@@ -453,7 +509,8 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
   m->pipe[1] = NU > 1 ? (float)(k_sum / (NU - 1)) : 0.0f;  // per masked part
   m->pipe[2] = NU > 1 ? (float)(t_masked / (NU - 1)) : 0.0f;
   m->pipe[3] = (float)m->enc_cus;
-  m->pipe_pairs = pairing ? NB / 2 : 0;
+  m->pipe_pairs = pairs;
+  m->pipe_units3 = units3;
   return WQ4_OK;
 }
 
@@ -520,6 +577,17 @@ wq4_status wa_last_pipeline_stats(const wa_model* m, float* out) {
 
 int wa_last_pipeline_pairs(const wa_model* m) { return m ? m->pipe_pairs : 0; }
 
+int wa_last_pipeline_units3(const wa_model* m) { return m ? m->pipe_units3 : 0; }
+
+wq4_status wa_pipeline_unit_sizes(int n_batches, int width, int* sizes, int* n_units) {
+  if (!sizes || !n_units) return fail(WQ4_EINVAL, "null argument");
+  if (n_batches < 1 || width < 1 || width > kMaxLanes) return fail(WQ4_EINVAL, "n_batches >= 1, width in [1, 3]");
+  const std::vector<int> s = unit_sizes(n_batches, width);
+  std::copy(s.begin(), s.end(), sizes);
+  *n_units = (int)s.size();
+  return WQ4_OK;
+}
+
 wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const int32_t* trace_ids_dev,
                                int trace_k, float* trace_out_dev, void* stream) {
@@ -534,11 +602,13 @@ wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, i
   m->trace_out = nullptr;
   m->trace_s1 = m->trace_k = 0;
   for (DecGroup& g : m->groups) {  // the trace graphs bake in the caller's buffers: never replay them again
-    for (hipGraphExec_t* x : {&g.graph, &g.graph_alt}) {
-      if (*x) (void)hipGraphExecDestroy(*x);
-      *x = nullptr;
+    if (g.graph) (void)hipGraphExecDestroy(g.graph);
+    g.graph = nullptr;
+    g.graph_key = -1;
+    for (DecGroup::KeptGraph& k : g.kept) {
+      if (k.exec) (void)hipGraphExecDestroy(k.exec);
+      k = DecGroup::KeptGraph{};
     }
-    g.graph_key = g.graph_alt_key = -1;
   }
   return s;
 }

@@ -45,6 +45,10 @@ def lib() -> ctypes.CDLL:
         L.wa_last_pipeline_stats.argtypes = [vp, f32p]
         L.wa_last_pipeline_pairs.argtypes = [vp]
         L.wa_last_pipeline_pairs.restype = c_int
+        L.wa_last_pipeline_units3.argtypes = [vp]
+        L.wa_last_pipeline_units3.restype = c_int
+        L.wa_pipeline_unit_sizes.argtypes = [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        L.wa_pipeline_unit_sizes.restype = c_int
         L.wa_encode.argtypes = [vp, vp, c_int, vp, vp]
         L.wa_prompt_logits.argtypes = [vp, vp, c_int, c_int, vp, vp]
         L.wa_synth_uniform.argtypes = [ctypes.c_uint64, ctypes.c_char_p, c_i64, ctypes.c_float, ctypes.c_float, f32p]
@@ -208,6 +212,15 @@ def xattn_plan_splits(T: int, rows: int, free_cus: int) -> tuple[int, int]:
     s, c = ctypes.c_int(), ctypes.c_int()
     check(lib().wa_xattn_plan_splits(T, rows, free_cus, ctypes.byref(s), ctypes.byref(c)))
     return s.value, c.value
+
+
+def pipeline_unit_sizes(n_batches: int, width: int) -> list[int]:
+    """Sizes, in order, of the units a transcribe_batches over n_batches
+    batches forms when up to `width` batches decode at once: the host rule
+    (wa_pipeline_unit_sizes), without the device's room for lanes."""
+    sizes, n = (ctypes.c_int * max(1, n_batches))(), ctypes.c_int()
+    check(lib().wa_pipeline_unit_sizes(n_batches, width, sizes, ctypes.byref(n)))
+    return [int(sizes[i]) for i in range(n.value)]
 
 
 def xattn_kv_check(q, k, v, Tq: int, precision: int = wq4.PREC_F16X2):
@@ -398,15 +411,22 @@ class WhisperModel:
 
     def pipeline_stats(self) -> dict:
         """After transcribe_batches: batches, mean encoder layers run beside a
-        decode, mean ms of that CU-masked part, CUs of the masked stream."""
+        decode, mean ms of that CU-masked part, CUs of the masked stream, and
+        the units of two and of three batches that decoded together."""
         t = (ctypes.c_float * 4)()
         check(lib().wa_last_pipeline_stats(self._h, t))
-        return {"batches": int(t[0]), "overlap_layers": t[1], "masked_ms": t[2], "masked_cus": int(t[3])}
+        return {"batches": int(t[0]), "overlap_layers": t[1], "masked_ms": t[2], "masked_cus": int(t[3]),
+                "pairs": self.pipeline_pairs(), "units3": self.pipeline_units3()}
 
     def pipeline_pairs(self) -> int:
         """Batch pairs the last transcribe_batches decoded together, one decode
         group per batch (wa_last_pipeline_pairs); 0: every batch on its own."""
         return int(lib().wa_last_pipeline_pairs(self._h))
+
+    def pipeline_units3(self) -> int:
+        """Units of three batches the last transcribe_batches decoded together
+        (wa_last_pipeline_units3); pipeline_pairs counts those of exactly two."""
+        return int(lib().wa_last_pipeline_units3(self._h))
 
     def decode_graph_key(self, group: int = 0) -> int:
         """Key of decode group `group`'s current step graph (wa_decode_graph_key; -1: none)."""
