@@ -132,10 +132,10 @@ wq4_status wa_self_attention_check(int device, const float* qkv_dev, float* cach
   });
 }
 
-wq4_status wa_logits_argmax_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
-                                  int step, wq4_precision prec, int32_t* tok_dev, float* logits_dev) {
-  if (!hid_dev || !emb_dev || !tok_dev) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || n_clips > 32 || V < 1 || !emb_tiled_supported(D)) return fail(WQ4_EINVAL, "bad sizes");
+// wa_logits_argmax_check, and with logprob_dev the scored launch of wa_logits_logprob_check
+static wq4_status logits_pick_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                    int step, wq4_precision prec, int32_t* tok_dev, float* logprob_dev,
+                                    float* logits_dev) {
   const int ns = planes(prec);
   WA_HIP(hipSetDevice(device));
   Dev d;
@@ -146,11 +146,12 @@ wq4_status wa_logits_argmax_check(int device, const float* hid_dev, const float*
   auto* pval = d.alloc<float>((size_t)32 * ng);
   auto* pidx = d.alloc<int>((size_t)32 * ng);
   auto* ctr = d.alloc<int>(1);
+  float* psum = logprob_dev ? d.alloc<float>((size_t)32 * ng) : nullptr;
   const size_t tb = wq4_atiled_bytes(n_clips, D, prec);
   auto* ht = d.alloc<_Float16>(tb / 2);
   int* ids = nullptr;
   if (logits_dev) ids = d.alloc<int>((size_t)n_clips * 2 * V);
-  if (!emb2 || !st || !pval || !pidx || !ctr || !ht || (logits_dev && !ids))
+  if (!emb2 || !st || !pval || !pidx || !ctr || !ht || (logits_dev && !ids) || (logprob_dev && !psum))
     return fail(WQ4_ENOMEM, "allocation failed");
   WA_HIP(launch_emb_tiled(emb_dev, V, D, ns, emb2, nullptr));
   WA_WQ4(wq4_tile_activations(hid_dev, n_clips, D, D, prec, ht, tb, nullptr));
@@ -170,12 +171,42 @@ wq4_status wa_logits_argmax_check(int device, const float* hid_dev, const float*
     tr = d.alloc<float>((size_t)n_clips * 2 * V);
     if (!tr) return fail(WQ4_ENOMEM, "allocation failed");
   }
-  WA_HIP(launch_logits_argmax(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, ctr, tok_dev, ids, tr, 2, V,
-                              nullptr, nullptr));
+  if (logprob_dev)
+    WA_HIP(launch_logits_argmax_scored(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, psum, ctr, tok_dev,
+                                       logprob_dev, ids, tr, 2, V, nullptr, nullptr));
+  else
+    WA_HIP(launch_logits_argmax(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, ctr, tok_dev, ids, tr, 2, V,
+                                nullptr, nullptr));
   if (logits_dev)
     for (int b = 0; b < n_clips; ++b)
       WA_HIP(hipMemcpy(logits_dev + (size_t)b * V, tr + ((size_t)b * 2 + 1) * V, (size_t)V * 4,
                        hipMemcpyDeviceToDevice));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+wq4_status wa_logits_argmax_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                  int step, wq4_precision prec, int32_t* tok_dev, float* logits_dev) {
+  if (!hid_dev || !emb_dev || !tok_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > 32 || V < 1 || !emb_tiled_supported(D)) return fail(WQ4_EINVAL, "bad sizes");
+  return logits_pick_check(device, hid_dev, emb_dev, n_clips, D, V, step, prec, tok_dev, nullptr, logits_dev);
+}
+
+wq4_status wa_logits_logprob_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                   int step, wq4_precision prec, int32_t* tok_dev, float* logprob_dev,
+                                   float* logits_dev) {
+  if (!hid_dev || !emb_dev || !tok_dev || !logprob_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > 32 || V < 1 || !emb_tiled_supported(D)) return fail(WQ4_EINVAL, "bad sizes");
+  return logits_pick_check(device, hid_dev, emb_dev, n_clips, D, V, step, prec, tok_dev, logprob_dev, logits_dev);
+}
+
+wq4_status wa_row_logprob_check(int device, const float* logits_dev, int n_rows, int V, int lo, int hi, int mask_eot,
+                                const int32_t* idx_dev, int fixed_idx, float* logprob_dev) {
+  if (!logits_dev || !logprob_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || n_rows > 32 || V < 1 || lo < 0 || hi > V || lo >= hi) return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  WA_HIP(launch_row_logprob(logits_dev, n_rows, V, lo, hi, mask_eot, 0, nullptr, idx_dev, 1, fixed_idx, logprob_dev, 1,
+                            nullptr));
   WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }

@@ -77,11 +77,21 @@ bool fused_pick(const DecGroup& g, int Tq, const DecodeState* state) {
 }
 
 // One greedy step (whisper.rs:104-125): bookkeeping, decode_step, argmax.
+// A scored transcribe (m->score) stores each pick's log-probability where its
+// token goes, and a stored-logits group scores its pick with the row kernel.
 wq4_status decode_step(wa_model* m, DecGroup& g, int eot_stop, hipStream_t st) {
-  WA_HIP(launch_bookkeep(g.next_tok, g.tokens, g.ntok, g.done, g.nb, kMaxTokens, eot_stop, g.state, st));
+  if (m->score)
+    WA_HIP(launch_bookkeep_scored(g.next_tok, g.next_lp, g.tokens, g.logprob, g.ntok, g.done, g.nb, kMaxTokens,
+                                  eot_stop, g.state, st));
+  else
+    WA_HIP(launch_bookkeep(g.next_tok, g.tokens, g.ntok, g.done, g.nb, kMaxTokens, eot_stop, g.state, st));
   WA_TRY(decoder_forward(m, g, g.next_tok, 1, g.state, 0, 0, st));
-  if (!fused_pick(g, 1, g.state))
+  if (!fused_pick(g, 1, g.state)) {
     WA_HIP(launch_argmax_step(g.logits, g.nb, m->cfg.n_vocab, kMinTokens, g.state, g.next_tok, m->range_flag, st));
+    if (m->score)
+      WA_HIP(launch_row_logprob(g.logits, g.nb, m->cfg.n_vocab, 0, m->cfg.n_vocab, 0, kMinTokens, g.state, g.next_tok,
+                                1, 0, g.next_lp, 1, st));
+  }
   return WQ4_OK;
 }
 
@@ -428,14 +438,44 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
     // embedding planes' precision)
     WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, m->prec, g.hid_t, nullptr, st));
     const size_t tofs = (size_t)g.b0 * m->trace_s1 * m->trace_k;
-    WA_HIP(launch_logits_argmax(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.lg_val, g.lg_idx,
-                                g.lg_ctr, g.next_tok, m->trace_out ? m->trace_ids + tofs : nullptr,
-                                m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k, m->range_flag,
-                                st));
+    if (m->score)  // the SCORE = 1 instantiation: the pick's log-probability beside it, into next_lp
+      WA_HIP(launch_logits_argmax_scored(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.lg_val,
+                                         g.lg_idx, g.lg_sum, g.lg_ctr, g.next_tok, g.next_lp,
+                                         m->trace_out ? m->trace_ids + tofs : nullptr,
+                                         m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
+                                         m->range_flag, st));
+    else
+      WA_HIP(launch_logits_argmax(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.lg_val, g.lg_idx,
+                                  g.lg_ctr, g.next_tok, m->trace_out ? m->trace_ids + tofs : nullptr,
+                                  m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
+                                  m->range_flag, st));
     return WQ4_OK;
   }
   WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, WQ4_PREC_F16X2, nullptr, g.hid, st));
   WA_HIP(launch_logits(g.hid + (size_t)(Tq - 1) * D, B, D, (int64_t)Tq * D, m->tok_emb, c.n_vocab, g.logits, st));
+  return WQ4_OK;
+}
+
+// The scores taken at the SOT position of group g's prompt, from its unmasked
+// logit rows z0 [nb][n_vocab]: the no-speech probability softmax(z0)
+// [no_speech] and the language token's probability among the language tokens
+// -- the token from lang_idx (stride lang_stride; the detected one) or the
+// caller's lang_fixed.
+static wq4_status score_sot(wa_model* m, DecGroup& g, const float* z0, const int* lang_idx, int lang_stride, int lang_fixed,
+                     hipStream_t st) {
+  const Config& c = m->cfg;
+  const int B = g.nb, V = c.n_vocab;
+  WA_HIP(launch_row_logprob(z0, B, V, 0, V, 0, 0, nullptr, nullptr, 0, c.no_speech_token(), g.no_speech, 1, st));
+  WA_HIP(launch_exp_inplace(g.no_speech, B, st));
+  WA_HIP(launch_row_logprob(z0, B, V, 50259, 50259 + c.n_lang, 0, 0, nullptr, lang_idx, lang_stride, lang_fixed,
+                            g.lang_prob, 1, st));
+  WA_HIP(launch_exp_inplace(g.lang_prob, B, st));
+  if (lang_idx) {
+    WA_HIP(launch_gather_int(lang_idx, lang_stride, g.lang_tok, B, st));
+  } else {
+    const std::vector<int> lt(B, lang_fixed);  // pageable: the copy is staged before the call returns
+    WA_HIP(hipMemcpyAsync(g.lang_tok, lt.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
+  }
   return WQ4_OK;
 }
 
@@ -455,6 +495,12 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
     }
     WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * 4 * 4, hipMemcpyHostToDevice, st));
     WA_TRY(decoder_forward(m, g, g.prompt_tok, 4, nullptr, 0, 0, st));
+    if (m->score) {
+      // z0, the SOT position's logits: row 0 of each clip's four final-LN rows
+      // in g.hid (by causality the single-SOT pass of the auto-detect prompt)
+      WA_HIP(launch_logits(g.hid, B, c.n_text_state, (int64_t)4 * c.n_text_state, m->tok_emb, c.n_vocab, g.z0, st));
+      WA_TRY(score_sot(m, g, g.z0, nullptr, 0, lang_token, st));
+    }
     pos0 = 4;
     kv0 = 4;
   } else {
@@ -473,6 +519,7 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
     WA_TRY(decoder_forward(m, g, g.next_tok, 1, nullptr, 0, 0, st));
     WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 50259, 50259 + c.n_lang, 0, nullptr, g.prompt_tok, 3, m->range_flag,
                          st));
+    if (m->score) WA_TRY(score_sot(m, g, g.logits, g.prompt_tok, 3, 0, st));  // before the next pass rewrites g.logits
     // ... then forward_prompt([lang, TRANSCRIBE, NO_TIMESTAMPS]) OVERWRITES the
     // cache from index 0 with positions 0..2 (decoder.rs:272-283) while the
     // position counter continues at 1 + 3 = 4 (whisper.rs:74,93).
@@ -482,6 +529,10 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
   }
   // first token: EOT suppressed (whisper.rs:97-99)
   WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, nullptr, g.next_tok, 1, m->range_flag, st));
+  if (m->score) {  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
+    WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st));
+    WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
+  }
   const DecodeState init{pos0 - 1, kv0 - 1, -1, 0};
   WA_HIP(hipMemcpyAsync(g.state, &init, sizeof(init), hipMemcpyHostToDevice, st));
   WA_HIP(hipMemsetAsync(g.ntok, 0, (size_t)B * 4, st));
@@ -499,7 +550,9 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
   // decodes in a pair recaptures); one explicit field per mixed-radix digit
   const int64_t key =
       ((((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
-         (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * 16 + g.xplan.splits) * (kXattnResDen + 1) + g.xres.q;
+         (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * 16 + g.xplan.splits) * (kXattnResDen + 1) + g.xres.q +
+      // scoring, the top digit (above every lane): an unscored key is what it was
+      (m->score ? (int64_t)kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0);
   if (g.graph && g.graph_key == key) return WQ4_OK;
   // the other layouts' graphs are kept: a call goes from units of three to
   // pairs or a lone last batch, beside the masked stream and without it, and
@@ -582,6 +635,40 @@ wq4_status ensure_ffn_ws(wa_model* m) {
   m->ffn_ws = e;
   m->ffn_ws_bytes = ne;
   m->bytes += ne;
+  return WQ4_OK;
+}
+
+// The score buffers of every decode group (DecGroup::next_lp ..), each sized
+// for the whole batch like the group's other buffers: allocated by the first
+// scored transcribe, all or nothing, never released.
+wq4_status ensure_score_buffers(wa_model* m) {
+  if (m->score_alloc_ok) return WQ4_OK;
+  const size_t B = (size_t)m->bmax, V = (size_t)m->cfg.n_vocab;
+  const size_t ng = (size_t)32 * logits_argmax_groups(m->cfg.n_vocab);
+  bool ok = true;
+  for (DecGroup& g : m->groups) {
+    g.next_lp = m->dev.alloc<float>(B);
+    g.logprob = m->dev.alloc<float>(B * (kMaxTokens + 1));
+    g.lg_sum = m->dev.alloc<float>(ng);
+    g.no_speech = m->dev.alloc<float>(B);
+    g.lang_prob = m->dev.alloc<float>(B);
+    g.lang_tok = m->dev.alloc<int>(B);
+    g.z0 = m->dev.alloc<float>(B * V);
+    ok = ok && g.next_lp && g.logprob && g.lg_sum && g.no_speech && g.lang_prob && g.lang_tok && g.z0;
+  }
+  if (!ok) {
+    (void)hipGetLastError();  // the failed hipMalloc is handled here
+    for (DecGroup& g : m->groups) {
+      for (void* p : {(void*)g.next_lp, (void*)g.logprob, (void*)g.lg_sum, (void*)g.no_speech, (void*)g.lang_prob,
+                      (void*)g.lang_tok, (void*)g.z0})
+        m->dev.release(p);
+      g.next_lp = g.logprob = g.lg_sum = g.no_speech = g.lang_prob = g.z0 = nullptr;
+      g.lang_tok = nullptr;
+    }
+    return fail(WQ4_ENOMEM, "score buffer allocation failed");
+  }
+  m->bytes += m->groups.size() * 4 * (B * (kMaxTokens + 1 + 4) + ng + B * V);
+  m->score_alloc_ok = true;
   return WQ4_OK;
 }
 

@@ -1028,10 +1028,22 @@ __device__ __forceinline__ void better_pair(float& bv, int& bi, float v, int i) 
 // Greedy pick of a workgroup's 32 x 128 logits block lg[clip][kLgPickLd]
 // (already masked), then the last-arriving workgroup's pick over all
 // workgroups' candidates.
+// SCORE = 1 (scored transcribes) also leaves the pick's log-probability
+// lp = z[tok] - logsumexp(z) = -log(sum_v exp(z[v] - M)), M = z[tok] the row
+// maximum, in out_lp[clip]: each workgroup adds, beside its candidate
+// (m_w, index), s_w = sum exp(z - m_w) over its 128 logits (psum, a third
+// [32][groups] scratch array, the same write-through stores ahead of the
+// ticket), and the last-arriving workgroup, which knows M, sums
+// S = sum_w s_w exp(m_w - M) and writes -log S.  A masked (-inf) logit adds
+// 0; two equal maxima add 1 each.  f32 throughout; the longest chain of
+// additions is 16 per thread + 3 shuffles + ceil(groups / 8) candidates + 3
+// shuffles (73 at V = 51866).  SCORE = 0 is the pick alone.
 constexpr int kLgPickLd = 132;
+template <int SCORE>
 __device__ __forceinline__ void pick_from_lds(const float* lg, int B, int V, float* __restrict__ pval,
-                                              int* __restrict__ pidx, int* __restrict__ counter,
-                                              int* __restrict__ out_tok, int* ticket) {
+                                              int* __restrict__ pidx, float* __restrict__ psum,
+                                              int* __restrict__ counter, int* __restrict__ out_tok,
+                                              float* __restrict__ out_lp, int* ticket) {
   const int tid = threadIdx.x, nwg = gridDim.x;
   __syncthreads();
   const int row = tid >> 3, part = tid & 7;
@@ -1051,6 +1063,25 @@ __device__ __forceinline__ void pick_from_lds(const float* lg, int B, int V, flo
   }
   const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(pval, 0, 32 * nwg * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(pidx, 0, 32 * nwg * 4, 0x00020000);
+  __amdgpu_buffer_rsrc_t rs = rv;
+  if constexpr (SCORE) {
+    // s_w over this workgroup's logits of the row, relative to its maximum
+    // bv (the same in the row's 8 threads); every logit masked: 0
+    float s = 0.0f;
+    if (bv > -INFINITY) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int c = part * 16 + j;
+        if (blockIdx.x * 128 + c < V) s += expf(lg[row * kLgPickLd + c] - bv);
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) s += __shfl_xor(s, o, 64);
+    rs = __builtin_amdgcn_make_buffer_rsrc(psum, 0, 32 * nwg * 4, 0x00020000);
+    if (part == 0 && row < B)
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s), rs,
+                                            (uint32_t)(row * nwg + blockIdx.x) * 4, 0, 16);  // sc1
+  }
   if (part == 0 && row < B) {
     const uint32_t off = (uint32_t)(row * nwg + blockIdx.x) * 4;
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, bv), rv, off, 0, 16);  // sc1
@@ -1083,6 +1114,21 @@ __device__ __forceinline__ void pick_from_lds(const float* lg, int B, int V, flo
     better_pair(bv, bi, v2, i2);
   }
   if (part == 0 && row < B) out_tok[row] = bi < 0 ? 0 : bi;
+  if constexpr (SCORE) {
+    // bv = M in the row's 8 threads: the candidates again, rescaled to it
+    float S = 0.0f;
+    if (row < B && bv > -INFINITY) {
+      for (int j = part; j < nwg; j += 8) {
+        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+        const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, off, 0, 16));
+        const float s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 16));
+        S += s * expf(v - bv);
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) S += __shfl_xor(S, o, 64);
+    if (part == 0 && row < B) out_lp[row] = -logf(S);
+  }
   if (tid == 0) {
     typedef __attribute__((address_space(1))) int gint;
     __hip_atomic_store((gint*)counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
@@ -1107,12 +1153,12 @@ __host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 12
 // (diagnostics, null in the product graph): the logits of
 // trace_ids[clip][step + 1][0..trace_k) are written to the same slots of
 // trace_out, as the pick sees them (EOT already masked).
-template <int NS>
+template <int NS, int SCORE = 0>
 __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
     const _Float16* __restrict__ htiled, int B, int D, const _Float16* __restrict__ emb2, int V, int min_tokens,
     const DecodeState* __restrict__ state, float* __restrict__ pval, int* __restrict__ pidx, int* __restrict__ counter,
     int* __restrict__ out_tok, const int* __restrict__ trace_ids, float* __restrict__ trace_out, int trace_s1,
-    int trace_k, int* __restrict__ range_flag) {
+    int trace_k, int* __restrict__ range_flag, float* __restrict__ psum, float* __restrict__ out_lp) {
   constexpr int KS = kLg2Chunk / 32;             // Q4-block-sized k-steps per chunk
   constexpr int HCH = KS * 2 * NS * 1024;        // bytes of hidden fragments per chunk
   static_assert(HCH % (256 * 16) == 0, "whole glds rounds");
@@ -1236,7 +1282,7 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
         if (id >= 0 && id < 128) trace_out[o] = lg[b * kLgPickLd + id];
       }
   }
-  pick_from_lds(lg, B, V, pval, pidx, counter, out_tok, ticket);
+  pick_from_lds<SCORE>(lg, B, V, pval, pidx, psum, counter, out_tok, out_lp, ticket);
 }
 
 int logits_argmax_groups(int V) { return (V + 127) / 128; }
@@ -1290,12 +1336,104 @@ hipError_t launch_logits_argmax(const _Float16* htiled, int B, int D, const _Flo
                                 int* range_flag, hipStream_t st) {
   if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled) return hipErrorInvalidValue;
   const dim3 grid(logits_argmax_groups(V));
+  float* const none = nullptr;
   if (ns == 2)
-    hipLaunchKernelGGL(logits_argmax_f16_k32_kernel<2>, grid, dim3(256), 0, st, htiled, B, D, emb2, V, min_tokens,
-                       state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k, range_flag);
+    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 0>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
+                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
+                       range_flag, none, none);
   else
-    hipLaunchKernelGGL(logits_argmax_f16_k32_kernel<1>, grid, dim3(256), 0, st, htiled, B, D, emb2, V, min_tokens,
-                       state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k, range_flag);
+    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 0>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
+                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
+                       range_flag, none, none);
+  return hipGetLastError();
+}
+
+hipError_t launch_logits_argmax_scored(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
+                                       int min_tokens, const DecodeState* state, float* pval, int* pidx, float* psum,
+                                       int* counter, int* out_tok, float* out_lp, const int* trace_ids,
+                                       float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st) {
+  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled || !psum || !out_lp)
+    return hipErrorInvalidValue;
+  const dim3 grid(logits_argmax_groups(V));
+  if (ns == 2)
+    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
+                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
+                       range_flag, psum, out_lp);
+  else
+    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
+                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
+                       range_flag, psum, out_lp);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------ row log-prob --
+// out[row * out_stride] = z[id] - logsumexp(z[lo:hi]) of the stored logit row
+// z = logits + row * ld, id = idx ? idx[row * idx_stride] : fixed_idx, EOT
+// treated as -inf when mask_eot (the pick's own masking, whisper.rs:97-98,
+// 120-122; mask_state: when mask_state->step + 1 < min_tokens instead).  One
+// workgroup per row, two passes over the range: the maximum, then
+// sum exp(z - max) -- per thread ceil((hi - lo) / 256) terms, 6 shuffle adds,
+// 3 adds over the waves -- and z[id] - max - log(sum).  A -inf entry adds 0;
+// an id outside [lo, hi) or a row with no finite entry gives NaN.
+__global__ __launch_bounds__(256) void row_logprob_kernel(const float* __restrict__ logits, int64_t ld, int lo, int hi,
+                                                          int mask_eot, int min_tokens,
+                                                          const DecodeState* __restrict__ mask_state,
+                                                          const int* __restrict__ idx, int idx_stride, int fixed_idx,
+                                                          float* __restrict__ out, int out_stride) {
+  __shared__ float sm[4];
+  __shared__ float ss[4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* z = logits + (size_t)b * ld;
+  const bool mask = mask_state ? (mask_state->step + 1 < min_tokens) : mask_eot != 0;
+  float m = -INFINITY;
+  for (int i = lo + tid; i < hi; i += 256) {
+    const float v = (mask && i == kEOT) ? -INFINITY : z[i];
+    m = fmaxf(m, v);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if (lane == 0) sm[wave] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+  float s = 0.0f;
+  if (m > -INFINITY)
+    for (int i = lo + tid; i < hi; i += 256) {
+      const float v = (mask && i == kEOT) ? -INFINITY : z[i];
+      s += expf(v - m);
+    }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) ss[wave] = s;
+  __syncthreads();
+  if (tid == 0) {
+    s = ((ss[0] + ss[1]) + ss[2]) + ss[3];
+    const int id = idx ? idx[(size_t)b * idx_stride] : fixed_idx;
+    float r = NAN;
+    if (id >= lo && id < hi && m > -INFINITY) {
+      const float v = (mask && id == kEOT) ? -INFINITY : z[id];
+      r = (v - m) - logf(s);
+    }
+    out[(size_t)b * out_stride] = r;
+  }
+}
+
+hipError_t launch_row_logprob(const float* logits, int rows, int64_t ld, int lo, int hi, int mask_eot, int min_tokens,
+                              const DecodeState* mask_state, const int* idx, int idx_stride, int fixed_idx, float* out,
+                              int out_stride, hipStream_t st) {
+  if (rows < 1 || lo < 0 || lo >= hi || hi > ld || !logits || !out) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(row_logprob_kernel, dim3(rows), dim3(256), 0, st, logits, ld, lo, hi, mask_eot, min_tokens,
+                     mask_state, idx, idx_stride, fixed_idx, out, out_stride);
+  return hipGetLastError();
+}
+
+// exp of every entry, in place (row log-probabilities -> probabilities)
+__global__ void exp_inplace_kernel(float* __restrict__ x, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] = expf(x[i]);
+}
+
+hipError_t launch_exp_inplace(float* x, int n, hipStream_t st) {
+  hipLaunchKernelGGL(exp_inplace_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n);
   return hipGetLastError();
 }
 
@@ -1325,6 +1463,55 @@ hipError_t launch_bookkeep(const int* next_tok, int* tokens, int* n_tokens, int*
                            int eot_stop, DecodeState* state, hipStream_t st) {
   hipLaunchKernelGGL(bookkeep_kernel, dim3(1), dim3(256), 0, st, next_tok, tokens, n_tokens, done, B, max_tokens,
                      eot_stop, state);
+  return hipGetLastError();
+}
+
+// bookkeep_kernel of a scored transcribe: the pick's log-probability next_lp[b]
+// goes where its token goes, logprob[b][ntok[b]] (rows of max_tokens + 1), and
+// the EOT pick that ends a clip leaves its own in the slot after the clip's
+// last token.
+__global__ void bookkeep_scored_kernel(const int* __restrict__ next, const float* __restrict__ next_lp,
+                                       int* __restrict__ tokens, float* __restrict__ logprob, int* __restrict__ ntok,
+                                       int* __restrict__ done, int B, int max_tokens, int eot_stop,
+                                       DecodeState* state) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    if (!done[b]) {
+      const int tk = next[b];
+      const float lp = next_lp[b];
+      if (eot_stop && tk == kEOT) {
+        done[b] = 1;
+        atomicAdd(&state->n_done, 1);
+        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
+      } else if (ntok[b] < max_tokens) {
+        tokens[(size_t)b * max_tokens + ntok[b]] = tk;
+        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
+        ntok[b] += 1;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    state->position += 1;
+    state->kv_len += 1;
+    state->step += 1;
+  }
+}
+
+hipError_t launch_bookkeep_scored(const int* next_tok, const float* next_lp, int* tokens, float* logprob,
+                                  int* n_tokens, int* done, int B, int max_tokens, int eot_stop, DecodeState* state,
+                                  hipStream_t st) {
+  hipLaunchKernelGGL(bookkeep_scored_kernel, dim3(1), dim3(256), 0, st, next_tok, next_lp, tokens, logprob, n_tokens,
+                     done, B, max_tokens, eot_stop, state);
+  return hipGetLastError();
+}
+
+// dst[i] = src[i * stride], i < n
+__global__ void gather_int_kernel(const int* __restrict__ src, int stride, int* __restrict__ dst, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[(size_t)i * stride];
+}
+
+hipError_t launch_gather_int(const int* src, int stride, int* dst, int n, hipStream_t st) {
+  hipLaunchKernelGGL(gather_int_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, stride, dst, n);
   return hipGetLastError();
 }
 

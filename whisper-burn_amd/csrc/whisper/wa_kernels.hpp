@@ -145,6 +145,29 @@ hipError_t launch_logits_argmax(const _Float16* htiled, int B, int D, const _Flo
                                 int min_tokens, const DecodeState* state, float* pval, int* pidx, int* counter,
                                 int* out_tok, const int* trace_ids, float* trace_out, int trace_s1, int trace_k,
                                 int* range_flag, hipStream_t st);
+// The same launch for a scored transcribe (wa_transcribe_scored): the kernel's
+// SCORE = 1 instantiation also writes out_lp[b] = log softmax(z_b)[out_tok[b]]
+// = -log sum_v exp(z_b[v] - max z_b) over the masked row the pick sees, from
+// per-workgroup partial sums in psum (a third 32 * logits_argmax_groups(V)
+// scratch array beside pval / pidx).  Rows >= B of out_lp are not written.
+hipError_t launch_logits_argmax_scored(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
+                                       int min_tokens, const DecodeState* state, float* pval, int* pidx, float* psum,
+                                       int* counter, int* out_tok, float* out_lp, const int* trace_ids,
+                                       float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st);
+// Log-probability of one entry of stored logit rows (the scores outside the
+// fused kernel: the prompt's pick, no-speech and language probabilities,
+// decode groups wider than 32 rows): out[r * out_stride] = z[id] -
+// logsumexp(z[lo:hi]), z = logits + r * ld, id = idx ? idx[r * idx_stride] :
+// fixed_idx.  EOT counts as -inf when mask_eot != 0 -- or, mask_state
+// non-null, when mask_state->step + 1 < min_tokens (whisper.rs:120-122).  An
+// id outside [lo, hi) gives NaN.
+hipError_t launch_row_logprob(const float* logits, int rows, int64_t ld, int lo, int hi, int mask_eot, int min_tokens,
+                              const DecodeState* mask_state, const int* idx, int idx_stride, int fixed_idx, float* out,
+                              int out_stride, hipStream_t st);
+// x[i] = exp(x[i]), i < n.
+hipError_t launch_exp_inplace(float* x, int n, hipStream_t st);
+// dst[i] = src[i * stride], i < n.
+hipError_t launch_gather_int(const int* src, int stride, int* dst, int n, hipStream_t st);
 // Whether the logits kernel reads a fragment-tiled table for this width.
 bool emb_tiled_supported(int D);
 // Rows of the fragment-tiled table (V padded to the kernel's 128-row groups).
@@ -163,6 +186,13 @@ hipError_t launch_emb_tiled(const float* emb, int V, int D, int ns, _Float16* ou
 // next token; then advance position / kv_len / step.
 hipError_t launch_bookkeep(const int* next_tok, int* tokens, int* n_tokens, int* done, int B, int max_tokens,
                            int eot_stop, DecodeState* state, hipStream_t st);
+
+// The same for a scored transcribe: next_lp[b], the log-probability of
+// next_tok[b], is stored beside the token in logprob [B][max_tokens + 1]; the
+// EOT pick that ends a clip leaves its own in the slot after the last token.
+hipError_t launch_bookkeep_scored(const int* next_tok, const float* next_lp, int* tokens, float* logprob,
+                                  int* n_tokens, int* done, int B, int max_tokens, int eot_stop, DecodeState* state,
+                                  hipStream_t st);
 
 // Step-dependent EOT suppression (whisper.rs:120-122) folded into argmax:
 // suppress iff state->step < min_tokens - 1 (state->step already advanced).

@@ -45,6 +45,7 @@ struct Config {  // WhisperConfig, src/model/config.rs:5-30
   int n_text_ctx, n_text_state, n_text_head, n_text_layer, n_vocab, n_lang;
   int transcribe_token() const { return 50260 + n_lang; }      // config.rs:66-69
   int no_timestamps_token() const { return transcribe_token() + 4; }  // config.rs:72-74
+  int no_speech_token() const { return no_timestamps_token() - 1; }   // <|nospeech|>, the token before it
 };
 
 struct Dev {
@@ -142,12 +143,21 @@ struct DecGroup {
   _Float16* hid_t;    // fused logits + argmax: the final LN, A-tiled (m-tile 0)
   float* lg_val;      //                        per-workgroup candidates [32][groups]
   int *lg_idx, *lg_ctr;
+  // scored transcribes (wa_transcribe_scored; allocated by the first one,
+  // ensure_score_buffers): the log-probability of next_tok, every stored
+  // pick's [nb][kMaxTokens + 1] (NaN where nothing was stored), the fused
+  // kernel's per-workgroup sums [32][groups], the prompt's no-speech and
+  // language probabilities with the language token, and the SOT position's
+  // logit rows [nb][n_vocab] of an explicit-language prompt
+  float *next_lp = nullptr, *logprob = nullptr, *lg_sum = nullptr;
+  float *no_speech = nullptr, *lang_prob = nullptr, *z0 = nullptr;
+  int* lang_tok = nullptr;
   DecodeState* state;
   void* ffn_ws = nullptr;  // range tier 2: wq4_ffn_forward_ws workspace (4 * nb rows)
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
+  int64_t graph_key = -1;  // (scoring, lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
   // graphs of other layouts this group ran (ensure_graph): a call of units of
   // three and two, with and without the masked stream beside them, goes
   // through four keys per group and comes back to each
@@ -243,6 +253,12 @@ struct wa_model {
   const int* trace_ids = nullptr;
   float* trace_out = nullptr;
   int trace_s1 = 0, trace_k = 0;
+  // a scored transcribe is running (wa_transcribe_scored /
+  // wa_transcribe_batches_scored; false otherwise): prompts and steps also
+  // leave the picks' log-probabilities, the no-speech and the language
+  // probability in the groups' score buffers
+  bool score = false;
+  bool score_alloc_ok = false;  // every group's score buffers allocated (ensure_score_buffers)
   // live kernel timing (wa_profile_*)
   struct Pending {
     hipEvent_t a, b;
@@ -310,6 +326,7 @@ wq4_status build_ln_fold(wa_model* m);
 void kv_config(wa_model* m, int max_batch);
 wq4_status alloc_activations(wa_model* m);
 wq4_status ensure_ffn_ws(wa_model* m);
+wq4_status ensure_score_buffers(wa_model* m);
 int decode_groups(int B);
 wq4_status encoder_front(wa_model* m, const float* mel, int B, hipStream_t st);
 wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);

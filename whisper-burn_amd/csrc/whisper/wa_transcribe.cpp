@@ -184,12 +184,19 @@ wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token,
   return WQ4_OK;
 }
 
+constexpr size_t kLpSlots = kMaxTokens + 1;  // log-probability slots per clip on the device
+// staged scores of a batch of B clips: [B][kLpSlots] log-probabilities, then
+// [B] no-speech probabilities, [B] language tokens (int32), [B] language probabilities
+size_t score_words(int B) { return (size_t)B * (kLpSlots + 3); }
+
 // `st` waits for every group of the run_decode, then copies the groups'
 // tokens / counts (kMaxTokens per clip) and the range flag to (pinned) host
 // memory: tok / nt / flag of the batch in lane 0; the batch in lane j of a
-// unit of n has its own j * lane_stride int32 further on in each.
+// unit of n has its own j * lane_stride int32 further on in each.  sc (a
+// scored transcribe; null otherwise): the batch's score_words(B) words of
+// scores, with the same lane stride.
 wq4_status collect_batch(wa_model* m, int B, int n, const hipEvent_t* gdone, hipStream_t st, int32_t* tok,
-                         int32_t* nt, int* flag, size_t lane_stride) {
+                         int32_t* nt, int* flag, size_t lane_stride, float* sc = nullptr) {
   const int G = unit_groups(B, n);
   for (int i = 0; i < G; ++i) WA_HIP(hipStreamWaitEvent(st, gdone[i], 0));
   for (int i = 0; i < G; ++i) {
@@ -198,6 +205,15 @@ wq4_status collect_batch(wa_model* m, int B, int n, const hipEvent_t* gdone, hip
     WA_HIP(hipMemcpyAsync(tok + ofs + (size_t)g.b0 * kMaxTokens, g.tokens, (size_t)g.nb * kMaxTokens * 4,
                           hipMemcpyDeviceToHost, st));
     WA_HIP(hipMemcpyAsync(nt + ofs + g.b0, g.ntok, (size_t)g.nb * 4, hipMemcpyDeviceToHost, st));
+    if (sc) {
+      float* s = sc + ofs;
+      const size_t nb4 = (size_t)g.nb * 4;
+      WA_HIP(hipMemcpyAsync(s + (size_t)g.b0 * kLpSlots, g.logprob, nb4 * kLpSlots, hipMemcpyDeviceToHost, st));
+      s += (size_t)B * kLpSlots;
+      WA_HIP(hipMemcpyAsync(s + g.b0, g.no_speech, nb4, hipMemcpyDeviceToHost, st));
+      WA_HIP(hipMemcpyAsync(s + B + g.b0, g.lang_tok, nb4, hipMemcpyDeviceToHost, st));
+      WA_HIP(hipMemcpyAsync(s + 2 * B + g.b0, g.lang_prob, nb4, hipMemcpyDeviceToHost, st));
+    }
   }
   // one flag word, set by any lane: a flagged unit flags all its batches
   for (int i = 0; i < n; ++i)
@@ -213,10 +229,25 @@ void copy_tokens(const int32_t* tok, const int32_t* nt, int B, int max_tokens, i
   }
 }
 
+// The staged scores `sc` of one batch (collect_batch) into the caller's
+// arrays at clip `clip0` of them: max_tokens + 1 slots per clip.
+void copy_scores(const float* sc, int B, int max_tokens, const wa_scores* out, size_t clip0) {
+  const float* s = sc + (size_t)B * kLpSlots;
+  if (out->token_logprob)
+    for (int b = 0; b < B; ++b)
+      std::memcpy(out->token_logprob + (clip0 + b) * (max_tokens + 1), sc + (size_t)b * kLpSlots,
+                  (size_t)(max_tokens + 1) * 4);
+  if (out->no_speech_prob) std::memcpy(out->no_speech_prob + clip0, s, (size_t)B * 4);
+  if (out->lang_token) std::memcpy(out->lang_token + clip0, s + B, (size_t)B * 4);
+  if (out->lang_prob) std::memcpy(out->lang_prob + clip0, s + 2 * B, (size_t)B * 4);
+}
+
 // One transcribe (whisper.rs:51-128 for a batch of clips); *overflow = the
-// range flag of this run (see wa_model::range_flag).
+// range flag of this run (see wa_model::range_flag).  scores (a scored
+// transcribe, m->score; null otherwise): this run's scores too.
 wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                           int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, bool* overflow) {
+                           int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, bool* overflow,
+                           const wa_scores* scores) {
   // all work on the model's own stream, ordered after the caller's stream
   hipStream_t st = m->own_stream;
   const int B = n_clips;
@@ -244,11 +275,13 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
   const int steps = *std::max_element(gsteps, gsteps + G);  // the last group to stop
   std::vector<int32_t> tok((size_t)B * kMaxTokens), nt(B);
   int flag = 0;
-  WA_TRY(collect_batch(m, B, 1, gdone, st, tok.data(), nt.data(), &flag, 0));
+  std::vector<float> sc(scores ? score_words(B) : 0);
+  WA_TRY(collect_batch(m, B, 1, gdone, st, tok.data(), nt.data(), &flag, 0, scores ? sc.data() : nullptr));
   WA_HIP(hipEventRecord(e_end, st));
   WA_HIP(hipStreamSynchronize(st));
   *overflow = flag != 0;
   copy_tokens(tok.data(), nt.data(), B, max_tokens, tokens_out, n_tokens_out);
+  if (scores) copy_scores(sc.data(), B, max_tokens, scores, 0);
   // phases: encoder, encoder planes (the cross-attention state), prompt (slowest group), decode loop
   float t_enc = 0.0f, t_kv = 0.0f, tp = 0.0f, tall = 0.0f;
   WA_HIP(hipEventElapsedTime(&t_enc, e_enc, e_kv));
@@ -326,7 +359,8 @@ wq4_status ensure_enc_stream(wa_model* m) {
 // call is cut into units by unit_sizes: widest first, and two units of two
 // in place of a unit of three and a lone batch.  One more group stream.
 wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B, int lang_token, int max_tokens,
-                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags) {
+                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags,
+                                const wa_scores* scores) {
   WA_TRY(ensure_enc_stream(m));
   hipStream_t st = m->own_stream, es = m->enc_stream;
   const int L = (int)m->enc.size();
@@ -342,9 +376,11 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
   const int widest = *std::max_element(sizes.begin(), sizes.end());
   const int lanes = ensure_lanes(m, widest);
   if (lanes < widest) sizes = unit_sizes(NB, lanes);
-  // pinned result staging: per batch the groups' tokens, counts and range flag
+  // pinned result staging: per batch the groups' tokens, counts and range
+  // flag, then (a scored call) its scores
   int32_t* host = nullptr;
-  const size_t per = (size_t)B * kMaxTokens + B + 1;
+  const size_t per0 = (size_t)B * kMaxTokens + B + 1;
+  const size_t per = per0 + (scores ? score_words(B) : 0);
   WA_HIP(hipHostMalloc(reinterpret_cast<void**>(&host), (size_t)NB * per * 4, 0));
   struct HostGuard {  // an early error return may leave copies into `p` queued: drain this model's streams first
     wa_model* m;
@@ -451,7 +487,7 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
                       u.gdone, u.gsteps));
     int32_t* hb = host + (size_t)u.first * per;
     WA_TRY(collect_batch(m, B, u.n, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
-                         per));
+                         per, scores ? reinterpret_cast<float*>(hb + per0) : nullptr));
     if (i + 1 < NU) {  // the rest of the next unit's encoder work at full width
       WA_HIP(hipStreamWaitEvent(st, u.mend, 0));
       WA_HIP(hipEventRecord(u.pstart, st));
@@ -465,6 +501,7 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
     copy_tokens(hb, hb + (size_t)B * kMaxTokens, B, max_tokens, tokens_out + (size_t)i * B * max_tokens,
                 n_tokens_out + (size_t)i * B);
     flags[i] = hb[(size_t)B * kMaxTokens + B];
+    if (scores) copy_scores(reinterpret_cast<const float*>(hb + per0), B, max_tokens, scores, (size_t)i * B);
   }
   // per-unit phases, averaged over the batches below: the exposed encoder,
   // prompt and decode times of a unit of n count 1 / n for each of its batches
@@ -518,12 +555,11 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
 
 extern "C" {
 
-wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                         int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  WA_HIP(hipSetDevice(m->device));
+// wa_transcribe, and wa_transcribe_scored with its scores: the scores are
+// those of the run whose tokens are returned.
+static wq4_status transcribe_tiers(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                   int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream,
+                                   const wa_scores* scores) {
   // A flagged run is retried one range tier up (wa_model::range_tier), sticky
   // for the model: its activations evidently exceed the range below.
   //   0 -> 1  the LayerNorm fold feeds the raw residual stream to the MFMAs
@@ -533,7 +569,7 @@ wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lan
   for (;;) {
     bool overflow = false;
     WA_TRY(transcribe_once(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
-                           &overflow));
+                           &overflow, scores));
     if (!overflow) return WQ4_OK;
     if (m->range_tier == 3)
       return fail(WQ4_ERANGE,
@@ -544,17 +580,38 @@ wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lan
   }
 }
 
-wq4_status wa_transcribe_batches(wa_model* m, const float* mel_dev, int n_batches, int n_clips, int lang_token,
-                                 int max_tokens, int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out,
-                                 void* stream) {
+wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                         int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream) {
   if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
-  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
   if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
   if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
   WA_HIP(hipSetDevice(m->device));
+  return transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
+                          nullptr);
+}
+
+wq4_status wa_transcribe_scored(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
+                                void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !scores) return fail(WQ4_EINVAL, "null argument");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  WA_HIP(hipSetDevice(m->device));
+  WA_TRY(ensure_score_buffers(m));
+  m->score = true;
+  const wq4_status s = transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
+                                        n_tokens_out, stream, scores);
+  m->score = false;
+  return s;
+}
+
+// wa_transcribe_batches, and wa_transcribe_batches_scored (m->score set) with its scores.
+static wq4_status transcribe_batches(wa_model* m, const float* mel_dev, int n_batches, int n_clips, int lang_token,
+                                     int max_tokens, int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out,
+                                     void* stream, const wa_scores* scores) {
   std::vector<int> flags(n_batches, 0);
   WA_TRY(transcribe_pipelined(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                              n_tokens_out, stream, flags.data()));
+                              n_tokens_out, stream, flags.data(), scores));
   const size_t mel_stride = (size_t)n_clips * m->cfg.n_mels * 2 * m->cfg.n_audio_ctx;
   // the pipeline decoded every batch at the tier the model had on entry
   const int tier0 = m->range_tier;
@@ -563,10 +620,47 @@ wq4_status wa_transcribe_batches(wa_model* m, const float* mel_dev, int n_batche
     // once that raised the (sticky) tier, the later batches are re-run at it
     // too -- one wa_transcribe per batch would have decoded them there
     if (!flags[i] && m->range_tier == tier0) continue;
-    WA_TRY(wa_transcribe(m, mel_dev + i * mel_stride, n_clips, lang_token, max_tokens, eot_stop,
-                         tokens_out + (size_t)i * n_clips * max_tokens, n_tokens_out + (size_t)i * n_clips, stream));
+    wa_scores at{};  // batch i's part of the caller's arrays
+    if (scores) {
+      const size_t c0 = (size_t)i * n_clips;
+      at.token_logprob = scores->token_logprob ? scores->token_logprob + c0 * (max_tokens + 1) : nullptr;
+      at.no_speech_prob = scores->no_speech_prob ? scores->no_speech_prob + c0 : nullptr;
+      at.lang_token = scores->lang_token ? scores->lang_token + c0 : nullptr;
+      at.lang_prob = scores->lang_prob ? scores->lang_prob + c0 : nullptr;
+    }
+    WA_TRY(transcribe_tiers(m, mel_dev + i * mel_stride, n_clips, lang_token, max_tokens, eot_stop,
+                            tokens_out + (size_t)i * n_clips * max_tokens, n_tokens_out + (size_t)i * n_clips, stream,
+                            scores ? &at : nullptr));
   }
   return WQ4_OK;
+}
+
+wq4_status wa_transcribe_batches(wa_model* m, const float* mel_dev, int n_batches, int n_clips, int lang_token,
+                                 int max_tokens, int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out,
+                                 void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
+  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  WA_HIP(hipSetDevice(m->device));
+  return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
+                            n_tokens_out, stream, nullptr);
+}
+
+wq4_status wa_transcribe_batches_scored(wa_model* m, const float* mel_dev, int n_batches, int n_clips,
+                                        int lang_token, int max_tokens, int eot_stop, int32_t* tokens_out,
+                                        int32_t* n_tokens_out, const wa_scores* scores, void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !scores) return fail(WQ4_EINVAL, "null argument");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  WA_HIP(hipSetDevice(m->device));
+  WA_TRY(ensure_score_buffers(m));
+  m->score = true;
+  const wq4_status s = transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop,
+                                          tokens_out, n_tokens_out, stream, scores);
+  m->score = false;
+  return s;
 }
 
 wq4_status wa_last_pipeline_stats(const wa_model* m, float* out) {

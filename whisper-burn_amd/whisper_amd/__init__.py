@@ -22,6 +22,13 @@ CFG_KEYS = ["n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_l
 _lib: Optional[ctypes.CDLL] = None
 
 
+class Scores(ctypes.Structure):
+    """struct wa_scores: host arrays, each nullable."""
+
+    _fields_ = [("token_logprob", ctypes.POINTER(ctypes.c_float)), ("no_speech_prob", ctypes.POINTER(ctypes.c_float)),
+                ("lang_token", ctypes.POINTER(ctypes.c_int32)), ("lang_prob", ctypes.POINTER(ctypes.c_float))]
+
+
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
@@ -93,6 +100,14 @@ def lib() -> ctypes.CDLL:
         L.wa_encoder_attention_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, vp]
         L.wa_self_attention_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
         L.wa_logits_argmax_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
+        sp = ctypes.POINTER(Scores)
+        L.wa_transcribe_scored.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
+        L.wa_transcribe_batches_scored.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
+        L.wa_logits_logprob_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp]
+        L.wa_row_logprob_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp]
+        for n in ("wa_transcribe_scored", "wa_transcribe_batches_scored", "wa_logits_logprob_check",
+                  "wa_row_logprob_check"):
+            getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
                   "wa_last_pipeline_stats", "wa_last_timings", "wa_encode",
@@ -281,6 +296,47 @@ def logits_argmax_check(hid, emb, step: int, precision: int = wq4.PREC_F16X2, wa
     return tok, lg
 
 
+def logits_logprob_check(hid, emb, step: int, precision: int = wq4.PREC_F16X2, want_logits: bool = True,
+                         logprob=None):
+    """The scored form of the decode step's fused logits + greedy pick
+    (wa_logits_logprob_check): hid cuda f32 [B, D], emb cuda f32 [V, D] ->
+    (tokens int32 [B], logprob f32 = log softmax(z)[token] over the masked
+    row the pick saw, logits [B, V] or None).  logprob: an optional cuda f32
+    buffer of >= B entries to write into (entries B .. stay untouched)."""
+    torch = _torch()
+    B, D = hid.shape
+    V = emb.shape[0]
+    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
+    lp = torch.empty(B, device=hid.device, dtype=torch.float32) if logprob is None else logprob
+    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32) if want_logits else None
+    check(lib().wa_logits_logprob_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
+                                        precision, _ptr(tok), _ptr(lp), _ptr(lg) if lg is not None else None))
+    return tok, lp, lg
+
+
+def row_logprob_check(logits, lo: int, hi: int, mask_eot: bool = False, idx=None, fixed_idx: int = 0):
+    """The row kernel of the stored-logits scores (wa_row_logprob_check):
+    logits cuda f32 [R, V] -> f32 [R], z[id] - logsumexp(z[lo:hi]) per row,
+    id = idx[row] (cuda int32 [R]) or fixed_idx; EOT counts as -inf with mask_eot."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    out = torch.empty(R, device=logits.device, dtype=torch.float32)
+    check(lib().wa_row_logprob_check(_dev(logits), _ptr(logits), R, V, lo, hi, 1 if mask_eot else 0,
+                                     _ptr(idx.contiguous()) if idx is not None else None, int(fixed_idx), _ptr(out)))
+    return out
+
+
+def _scored_clip(toks, n, lp, ns, lt, lpr) -> dict:
+    """One clip of a scored transcribe: lp its max_tokens + 1 log-probability slots."""
+    n = int(n)
+    k = n + 1 if n < len(lp) and not np.isnan(lp[n]) else n  # the EOT pick's slot, when the clip stopped on EOT
+    seen = lp[~np.isnan(lp)]
+    return {"tokens": toks[:n].tolist(), "token_logprob": lp[:k].copy(),
+            "avg_logprob": float(seen.astype(np.float64).mean()) if seen.size else float("nan"),
+            "no_speech_prob": float(ns), "lang_token": int(lt), "lang_prob": float(lpr), "logprob_slots": lp.copy()}
+
+
 class GgufReader:
     """GgufReader (src/gguf/reader.rs): header, tensor index, tensor bytes."""
 
@@ -408,6 +464,48 @@ class WhisperModel:
                                           1 if eot_stop else 0, toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p),
                                           self._stream()))
         return [[toks[i, b, : nt[i, b]].tolist() for b in range(B)] for i in range(NB)]
+
+    def _scored(self, mels, NB: Optional[int], lang_token, max_tokens: int, eot_stop: bool):
+        torch = _torch()
+        mels = mels.contiguous()
+        assert mels.dtype == torch.float32 and mels.is_cuda
+        B = mels.shape[0] if NB is None else mels.shape[1]
+        n = B * (NB or 1)
+        toks = np.zeros((n, max_tokens), np.int32)
+        nt = np.zeros(n, np.int32)
+        lp = np.zeros((n, max_tokens + 1), np.float32)
+        ns, lpr, lt = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        sc = Scores(lp.ctypes.data_as(f32p), ns.ctypes.data_as(f32p), lt.ctypes.data_as(i32p),
+                    lpr.ctypes.data_as(f32p))
+        lang = -1 if lang_token is None else int(lang_token)
+        if NB is None:
+            check(lib().wa_transcribe_scored(self._h, _ptr(mels), B, lang, max_tokens, 1 if eot_stop else 0,
+                                             toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), ctypes.byref(sc),
+                                             self._stream()))
+        else:
+            check(lib().wa_transcribe_batches_scored(self._h, _ptr(mels), NB, B, lang, max_tokens,
+                                                     1 if eot_stop else 0, toks.ctypes.data_as(i32p),
+                                                     nt.ctypes.data_as(i32p), ctypes.byref(sc), self._stream()))
+        clips = [_scored_clip(toks[i], nt[i], lp[i], ns[i], lt[i], lpr[i]) for i in range(n)]
+        return clips if NB is None else [clips[i * B:(i + 1) * B] for i in range(NB)]
+
+    def transcribe_scored(self, mel, lang_token: Optional[int] = 50259, max_tokens: int = 224,
+                          eot_stop: bool = True) -> list[dict]:
+        """transcribe with the scores of wa_transcribe_scored.  Per clip a dict:
+        tokens (as transcribe), token_logprob (float32, one per token, plus the
+        EOT pick's when the clip stopped on EOT), avg_logprob (their mean: the
+        sum over len + 1 when the clip ended on EOT), no_speech_prob,
+        lang_token, lang_prob, and logprob_slots (the raw max_tokens + 1
+        slots, NaN where nothing was stored)."""
+        return self._scored(mel, None, lang_token, max_tokens, eot_stop)
+
+    def transcribe_batches_scored(self, mels, lang_token: Optional[int] = 50259, max_tokens: int = 224,
+                                  eot_stop: bool = True) -> list[list[dict]]:
+        """transcribe_batches with scores (wa_transcribe_batches_scored): mels
+        cuda f32 [NB, B, n_mels, 3000] -> NB lists of B dicts as transcribe_scored."""
+        assert mels.dim() == 4
+        return self._scored(mels, mels.shape[0], lang_token, max_tokens, eot_stop)
 
     def pipeline_stats(self) -> dict:
         """After transcribe_batches: batches, mean encoder layers run beside a
