@@ -132,10 +132,13 @@ wq4_status wa_self_attention_check(int device, const float* qkv_dev, float* cach
   });
 }
 
-// wa_logits_argmax_check, and with logprob_dev the scored launch of wa_logits_logprob_check
+// wa_logits_argmax_check, with logprob_dev the scored launch of
+// wa_logits_logprob_check, and with rules_host (n_clips records) the
+// timestamp launch of wa_logits_timestamp_check
 static wq4_status logits_pick_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
                                     int step, wq4_precision prec, int32_t* tok_dev, float* logprob_dev,
-                                    float* logits_dev) {
+                                    float* logits_dev, const TsRule* rules_host = nullptr, int ts0 = 0,
+                                    int32_t* mass_dev = nullptr) {
   const int ns = planes(prec);
   WA_HIP(hipSetDevice(device));
   Dev d;
@@ -153,6 +156,17 @@ static wq4_status logits_pick_check(int device, const float* hid_dev, const floa
   if (logits_dev) ids = d.alloc<int>((size_t)n_clips * 2 * V);
   if (!emb2 || !st || !pval || !pidx || !ctr || !ht || (logits_dev && !ids) || (logprob_dev && !psum))
     return fail(WQ4_ENOMEM, "allocation failed");
+  TsRule* rules = nullptr;
+  float *xval = nullptr, *xsum = nullptr;
+  int* xidx = nullptr;
+  if (rules_host) {
+    rules = d.alloc<TsRule>(n_clips);
+    xval = d.alloc<float>((size_t)32 * ng);
+    xidx = d.alloc<int>((size_t)32 * ng);
+    xsum = d.alloc<float>((size_t)32 * ng);
+    if (!rules || !xval || !xidx || !xsum) return fail(WQ4_ENOMEM, "allocation failed");
+    WA_HIP(hipMemcpy(rules, rules_host, (size_t)n_clips * sizeof(TsRule), hipMemcpyHostToDevice));
+  }
   WA_HIP(launch_emb_tiled(emb_dev, V, D, ns, emb2, nullptr));
   WA_WQ4(wq4_tile_activations(hid_dev, n_clips, D, D, prec, ht, tb, nullptr));
   // A trace writes slot state->step + 1 of [clip][2][V] (every id listed at
@@ -171,7 +185,10 @@ static wq4_status logits_pick_check(int device, const float* hid_dev, const floa
     tr = d.alloc<float>((size_t)n_clips * 2 * V);
     if (!tr) return fail(WQ4_ENOMEM, "allocation failed");
   }
-  if (logprob_dev)
+  if (rules_host)
+    WA_HIP(launch_logits_argmax_ts(ht, n_clips, D, emb2, ns, V, min_tokens, st, rules, ts0, pval, pidx, psum, xval, xidx,
+                                   xsum, ctr, tok_dev, logprob_dev, mass_dev, ids, tr, 2, V, nullptr, nullptr));
+  else if (logprob_dev)
     WA_HIP(launch_logits_argmax_scored(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, psum, ctr, tok_dev,
                                        logprob_dev, ids, tr, 2, V, nullptr, nullptr));
   else
@@ -208,6 +225,74 @@ wq4_status wa_row_logprob_check(int device, const float* logits_dev, int n_rows,
   WA_HIP(launch_row_logprob(logits_dev, n_rows, V, lo, hi, mask_eot, 0, nullptr, idx_dev, 1, fixed_idx, logprob_dev, 1,
                             nullptr));
   WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+// ---- timestamp rules: the product kernels on caller data -----------------
+static_assert(sizeof(TsRule) == 8 * sizeof(int32_t), "a rule record is 8 int32 at the ABI");
+
+wq4_status wa_timestamp_rule(const int32_t* tokens, int n, int ts0, int V, int max_initial, int32_t* record_out) {
+  if (!record_out || n < 0 || (n > 0 && !tokens) || ts0 < 1 || V < ts0) return fail(WQ4_EINVAL, "bad arguments");
+  TsRule r = ts_rule_first(ts0, V, max_initial);
+  for (int i = 0; i < n; ++i) r = ts_rule_next(r, tokens[i], ts0, V);
+  std::memcpy(record_out, &r, sizeof(r));
+  return WQ4_OK;
+}
+
+wq4_status wa_logits_timestamp_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                     int step, wq4_precision prec, int ts0, const int32_t* records, int32_t* tok_dev,
+                                     float* logprob_dev, int32_t* mass_dev, float* logits_dev) {
+  if (!hid_dev || !emb_dev || !tok_dev || !logprob_dev || !records) return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > 32 || V < 1 || ts0 < 1 || !emb_tiled_supported(D)) return fail(WQ4_EINVAL, "bad sizes");
+  return logits_pick_check(device, hid_dev, emb_dev, n_clips, D, V, step, prec, tok_dev, logprob_dev, logits_dev,
+                           reinterpret_cast<const TsRule*>(records), ts0, mass_dev);
+}
+
+wq4_status wa_row_timestamp_check(int device, const float* logits_dev, int n_rows, int V, int suppress_eot, int ts0,
+                                  const int32_t* records, int32_t* tok_dev, float* logprob_dev, int32_t* mass_dev) {
+  if (!logits_dev || !records || !tok_dev || !logprob_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || n_rows > 32 || V < 1 || ts0 < 1) return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  auto* rules = d.alloc<TsRule>(n_rows);
+  if (!rules) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
+  WA_HIP(launch_row_timestamp(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, tok_dev, logprob_dev,
+                              mass_dev, nullptr, nullptr));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+wq4_status wa_timestamp_bookkeep_check(int device, const int32_t* tokens, int n_rows, int n_steps, int ts0, int V,
+                                       int max_initial, int32_t* records_out) {
+  if (!tokens || !records_out) return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || n_rows > 256 || n_steps < 1 || n_steps > kMaxTokens || ts0 < 1 || V < ts0)
+    return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  const size_t B = (size_t)n_rows;
+  auto* rules = d.alloc<TsRule>(B);
+  auto* next = d.alloc<int>(B);
+  auto* lp = d.alloc<float>(B);
+  auto* toks = d.alloc<int>(B * kMaxTokens);
+  auto* logprob = d.alloc<float>(B * (kMaxTokens + 1));
+  auto* ntok = d.alloc<int>(B);
+  auto* done = d.alloc<int>(B);
+  auto* st = d.alloc<DecodeState>(1);
+  if (!rules || !next || !lp || !toks || !logprob || !ntok || !done || !st) return fail(WQ4_ENOMEM, "allocation failed");
+  const std::vector<TsRule> first(B, ts_rule_first(ts0, V, max_initial));
+  WA_HIP(hipMemcpy(rules, first.data(), B * sizeof(TsRule), hipMemcpyHostToDevice));
+  WA_HIP(hipMemset(lp, 0, B * 4));
+  WA_HIP(hipMemset(ntok, 0, B * 4));
+  WA_HIP(hipMemset(done, 0, B * 4));
+  WA_HIP(hipMemset(st, 0, sizeof(DecodeState)));
+  std::vector<int> col(B);
+  for (int s = 0; s < n_steps; ++s) {  // one token per row and launch, as a decode step feeds them
+    for (size_t b = 0; b < B; ++b) col[b] = tokens[b * n_steps + s];
+    WA_HIP(hipMemcpy(next, col.data(), B * 4, hipMemcpyHostToDevice));
+    WA_HIP(launch_bookkeep_ts(next, lp, toks, logprob, ntok, done, n_rows, kMaxTokens, 0, st, rules, ts0, V, nullptr));
+    WA_HIP(hipMemcpy(records_out + (size_t)s * B * 8, rules, B * sizeof(TsRule), hipMemcpyDeviceToHost));
+  }
   return WQ4_OK;
 }
 

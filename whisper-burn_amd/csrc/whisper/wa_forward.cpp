@@ -79,14 +79,22 @@ bool fused_pick(const DecGroup& g, int Tq, const DecodeState* state) {
 // One greedy step (whisper.rs:104-125): bookkeeping, decode_step, argmax.
 // A scored transcribe (m->score) stores each pick's log-probability where its
 // token goes, and a stored-logits group scores its pick with the row kernel.
+// A timestamp transcribe (m->ts) also advances the clips' rule records in its
+// bookkeeping and picks under them (the TS fused launch, or the row kernel).
 wq4_status decode_step(wa_model* m, DecGroup& g, int eot_stop, hipStream_t st) {
-  if (m->score)
+  if (m->ts)
+    WA_HIP(launch_bookkeep_ts(g.next_tok, g.next_lp, g.tokens, g.logprob, g.ntok, g.done, g.nb, kMaxTokens, eot_stop,
+                              g.state, g.ts_rules, m->ts0(), m->cfg.n_vocab, st));
+  else if (m->score)
     WA_HIP(launch_bookkeep_scored(g.next_tok, g.next_lp, g.tokens, g.logprob, g.ntok, g.done, g.nb, kMaxTokens,
                                   eot_stop, g.state, st));
   else
     WA_HIP(launch_bookkeep(g.next_tok, g.tokens, g.ntok, g.done, g.nb, kMaxTokens, eot_stop, g.state, st));
   WA_TRY(decoder_forward(m, g, g.next_tok, 1, g.state, 0, 0, st));
-  if (!fused_pick(g, 1, g.state)) {
+  if (!fused_pick(g, 1, g.state) && m->ts) {  // the timestamp rule over the stored rows
+    WA_HIP(launch_row_timestamp(g.logits, g.nb, m->cfg.n_vocab, m->cfg.n_vocab, 0, kMinTokens, g.state, g.ts_rules,
+                                m->ts0(), g.next_tok, g.next_lp, nullptr, m->range_flag, st));
+  } else if (!fused_pick(g, 1, g.state)) {
     WA_HIP(launch_argmax_step(g.logits, g.nb, m->cfg.n_vocab, kMinTokens, g.state, g.next_tok, m->range_flag, st));
     if (m->score)
       WA_HIP(launch_row_logprob(g.logits, g.nb, m->cfg.n_vocab, 0, m->cfg.n_vocab, 0, kMinTokens, g.state, g.next_tok,
@@ -438,7 +446,13 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
     // embedding planes' precision)
     WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, m->prec, g.hid_t, nullptr, st));
     const size_t tofs = (size_t)g.b0 * m->trace_s1 * m->trace_k;
-    if (m->score)  // the SCORE = 1 instantiation: the pick's log-probability beside it, into next_lp
+    if (m->ts)  // the TS instantiation: the rows' rule records applied, the pick and its log-probability
+      WA_HIP(launch_logits_argmax_ts(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.ts_rules,
+                                     m->ts0(), g.lg_val, g.lg_idx, g.lg_sum, g.lg_xval, g.lg_xidx, g.lg_xsum, g.lg_ctr,
+                                     g.next_tok, g.next_lp, nullptr, m->trace_out ? m->trace_ids + tofs : nullptr,
+                                     m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
+                                     m->range_flag, st));
+    else if (m->score)  // the SCORE = 1 instantiation: the pick's log-probability beside it, into next_lp
       WA_HIP(launch_logits_argmax_scored(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.lg_val,
                                          g.lg_idx, g.lg_sum, g.lg_ctr, g.next_tok, g.next_lp,
                                          m->trace_out ? m->trace_ids + tofs : nullptr,
@@ -484,54 +498,69 @@ static wq4_status score_sot(wa_model* m, DecGroup& g, const float* z0, const int
 wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st) {
   const Config& c = m->cfg;
   const int B = g.nb;
+  // a timestamp transcribe's prompt ends at TRANSCRIBE: no NO_TIMESTAMPS
+  const int tail = m->ts ? 1 : 2;  // prompt tokens after the language token
   std::vector<int> ptok((size_t)B * 4);
   int pos0, kv0;
   if (lang_token >= 0) {
+    const int plen = 2 + tail;
     for (int b = 0; b < B; ++b) {
-      ptok[b * 4 + 0] = kSOT;
-      ptok[b * 4 + 1] = lang_token;
-      ptok[b * 4 + 2] = c.transcribe_token();
-      ptok[b * 4 + 3] = c.no_timestamps_token();
+      ptok[b * plen + 0] = kSOT;
+      ptok[b * plen + 1] = lang_token;
+      ptok[b * plen + 2] = c.transcribe_token();
+      if (!m->ts) ptok[b * plen + 3] = c.no_timestamps_token();
     }
-    WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * 4 * 4, hipMemcpyHostToDevice, st));
-    WA_TRY(decoder_forward(m, g, g.prompt_tok, 4, nullptr, 0, 0, st));
+    WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * plen * 4, hipMemcpyHostToDevice, st));
+    WA_TRY(decoder_forward(m, g, g.prompt_tok, plen, nullptr, 0, 0, st));
     if (m->score) {
-      // z0, the SOT position's logits: row 0 of each clip's four final-LN rows
-      // in g.hid (by causality the single-SOT pass of the auto-detect prompt)
-      WA_HIP(launch_logits(g.hid, B, c.n_text_state, (int64_t)4 * c.n_text_state, m->tok_emb, c.n_vocab, g.z0, st));
+      // z0, the SOT position's logits: row 0 of each clip's final-LN rows in
+      // g.hid (by causality the single-SOT pass of the auto-detect prompt)
+      WA_HIP(launch_logits(g.hid, B, c.n_text_state, (int64_t)plen * c.n_text_state, m->tok_emb, c.n_vocab, g.z0, st));
       WA_TRY(score_sot(m, g, g.z0, nullptr, 0, lang_token, st));
     }
-    pos0 = 4;
-    kv0 = 4;
+    pos0 = plen;
+    kv0 = plen;
   } else {
     // decode_step(SOT, 0) fills a 1-entry cache; the language is the last max
     // over the language-token range (whisper.rs:73-83) ...
+    const int plen = 1 + tail;
     for (int b = 0; b < B; ++b) {
-      ptok[b * 3 + 0] = kSOT;
-      ptok[b * 3 + 1] = c.transcribe_token();
-      ptok[b * 3 + 2] = c.no_timestamps_token();
+      ptok[b * plen + 0] = kSOT;
+      ptok[b * plen + 1] = c.transcribe_token();
+      if (!m->ts) ptok[b * plen + 2] = c.no_timestamps_token();
     }
-    WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * 3 * 4, hipMemcpyHostToDevice, st));
+    WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * plen * 4, hipMemcpyHostToDevice, st));
     // SOT rows: embed reads tokens[b * Tq + t] with Tq = 1 -> a contiguous [B]
     // array: next_tok as scratch
     std::vector<int> sot(B, kSOT);
     WA_HIP(hipMemcpyAsync(g.next_tok, sot.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
     WA_TRY(decoder_forward(m, g, g.next_tok, 1, nullptr, 0, 0, st));
-    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 50259, 50259 + c.n_lang, 0, nullptr, g.prompt_tok, 3, m->range_flag,
-                         st));
-    if (m->score) WA_TRY(score_sot(m, g, g.logits, g.prompt_tok, 3, 0, st));  // before the next pass rewrites g.logits
+    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 50259, 50259 + c.n_lang, 0, nullptr, g.prompt_tok, plen,
+                         m->range_flag, st));
+    if (m->score) WA_TRY(score_sot(m, g, g.logits, g.prompt_tok, plen, 0, st));  // before the next pass rewrites g.logits
     // ... then forward_prompt([lang, TRANSCRIBE, NO_TIMESTAMPS]) OVERWRITES the
     // cache from index 0 with positions 0..2 (decoder.rs:272-283) while the
-    // position counter continues at 1 + 3 = 4 (whisper.rs:74,93).
-    WA_TRY(decoder_forward(m, g, g.prompt_tok, 3, nullptr, 0, 0, st));
-    pos0 = 4;
-    kv0 = 3;
+    // position counter continues at 1 + 3 = 4 (whisper.rs:74,93) -- without
+    // NO_TIMESTAMPS: positions 0..1, the counter at 1 + 2.
+    WA_TRY(decoder_forward(m, g, g.prompt_tok, plen, nullptr, 0, 0, st));
+    pos0 = 1 + plen;
+    kv0 = plen;
   }
-  // first token: EOT suppressed (whisper.rs:97-99)
-  WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, nullptr, g.next_tok, 1, m->range_flag, st));
-  if (m->score) {  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
-    WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st));
+  if (m->ts) {
+    // every clip's rule record back to the empty history, then the first pick
+    // under it (rule e; EOT is masked with the text) and its log-probability
+    const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, m->ts_max_initial));  // pageable: staged
+    WA_HIP(hipMemcpyAsync(g.ts_rules, first.data(), (size_t)B * sizeof(TsRule), hipMemcpyHostToDevice, st));
+    WA_HIP(launch_row_timestamp(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, g.ts_rules, m->ts0(), g.next_tok,
+                                g.next_lp, nullptr, m->range_flag, st));
     WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
+  } else {
+    // first token: EOT suppressed (whisper.rs:97-99)
+    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, nullptr, g.next_tok, 1, m->range_flag, st));
+    if (m->score) {  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
+      WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st));
+      WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
+    }
   }
   const DecodeState init{pos0 - 1, kv0 - 1, -1, 0};
   WA_HIP(hipMemcpyAsync(g.state, &init, sizeof(init), hipMemcpyHostToDevice, st));
@@ -552,7 +581,9 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
       ((((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
          (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * 16 + g.xplan.splits) * (kXattnResDen + 1) + g.xres.q +
       // scoring, the top digit (above every lane): an unscored key is what it was
-      (m->score ? (int64_t)kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0);
+      (m->score ? (int64_t)kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0) +
+      // timestamps, the digit above it: the rule's max_initial is in the records, not in the graph
+      (m->ts ? (int64_t)2 * kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0);
   if (g.graph && g.graph_key == key) return WQ4_OK;
   // the other layouts' graphs are kept: a call goes from units of three to
   // pairs or a lone last batch, beside the masked stream and without it, and
@@ -669,6 +700,35 @@ wq4_status ensure_score_buffers(wa_model* m) {
   }
   m->bytes += m->groups.size() * 4 * (B * (kMaxTokens + 1 + 4) + ng + B * V);
   m->score_alloc_ok = true;
+  return WQ4_OK;
+}
+
+// The timestamp buffers of every decode group (DecGroup::ts_rules ..):
+// allocated by the first timestamp transcribe, all or nothing, never released.
+wq4_status ensure_ts_buffers(wa_model* m) {
+  if (m->ts_alloc_ok) return WQ4_OK;
+  const size_t B = (size_t)m->bmax;
+  const size_t ng = (size_t)32 * logits_argmax_groups(m->cfg.n_vocab);
+  bool ok = true;
+  for (DecGroup& g : m->groups) {
+    g.ts_rules = m->dev.alloc<TsRule>(B);
+    g.lg_xval = m->dev.alloc<float>(ng);
+    g.lg_xidx = m->dev.alloc<int>(ng);
+    g.lg_xsum = m->dev.alloc<float>(ng);
+    ok = ok && g.ts_rules && g.lg_xval && g.lg_xidx && g.lg_xsum;
+  }
+  if (!ok) {
+    (void)hipGetLastError();  // the failed hipMalloc is handled here
+    for (DecGroup& g : m->groups) {
+      for (void* p : {(void*)g.ts_rules, (void*)g.lg_xval, (void*)g.lg_xidx, (void*)g.lg_xsum}) m->dev.release(p);
+      g.ts_rules = nullptr;
+      g.lg_xval = g.lg_xsum = nullptr;
+      g.lg_xidx = nullptr;
+    }
+    return fail(WQ4_ENOMEM, "timestamp buffer allocation failed");
+  }
+  m->bytes += m->groups.size() * (B * sizeof(TsRule) + 3 * ng * 4);
+  m->ts_alloc_ok = true;
   return WQ4_OK;
 }
 

@@ -1135,6 +1135,238 @@ __device__ __forceinline__ void pick_from_lds(const float* lg, int B, int V, flo
   }
 }
 
+// ------------------------------------------------- timestamp rules --
+// The rule record's history update (TsRule, wa_kernels.hpp): the one
+// statement of rules c and d, shared by the bookkeeping kernel and the host.
+__host__ __device__ inline TsRule ts_rule_step(const TsRule& r, int tok, int ts0, int V) {
+  TsRule n;
+  n.first = 0;
+  n.penult = (r.first || r.last) ? 1 : 0;
+  n.last = tok >= ts0 ? 1 : 0;
+  n.t_last = n.last ? tok : r.t_last;
+  n.ts_hi = V - 1;
+  if (n.last && n.penult) {  // a closed pair (or a lone first timestamp): text next, no timestamp
+    n.text_ok = 1;
+    n.ts_lo = V;
+  } else if (n.last) {  // text then a timestamp: its partner (>= it) or EOT
+    n.text_ok = 0;
+    n.ts_lo = n.t_last;
+  } else {  // text: more text, or a timestamp past the last one
+    n.text_ok = 1;
+    n.ts_lo = n.t_last >= 0 ? n.t_last + 1 : ts0;
+  }
+  n.pad = 0;
+  return n;
+}
+
+TsRule ts_rule_first(int ts0, int V, int max_initial) {
+  TsRule r{};
+  r.text_ok = 0;
+  r.ts_lo = ts0;
+  r.ts_hi = max_initial < 0 ? V - 1 : (int)std::min<int64_t>(V - 1, (int64_t)ts0 + max_initial);
+  r.first = 1;
+  r.last = 0;
+  r.penult = 1;
+  r.t_last = -1;
+  return r;
+}
+
+TsRule ts_rule_next(const TsRule& r, int tok, int ts0, int V) { return ts_rule_step(r, tok, ts0, V); }
+
+// Masks a-e for one id of a row: r = the record's (text_ok, ts_lo, ts_hi,
+// first).  The one statement of the masks, shared by the fused and the
+// stored-logits pick.
+__device__ __forceinline__ bool ts_masked(int id, int ts0, const int4& r, bool suppress_eot) {
+  if (id >= ts0) return id < r.y || id > r.z;        // timestamps: the allowed range only (c, d, e)
+  if (id > kEOT) return true;                         // the specials (b)
+  if (id == kEOT) return suppress_eot || r.w != 0;    // a, and the first pick (e)
+  return r.x == 0;                                    // text (c, e)
+}
+
+// The mass rule and the pick from a row's two sides: (mt, it) the best text
+// candidate with st = sum exp(z - mt) over the text side, (mx, ix, sx) the
+// same over the timestamps; a side with nothing allowed is (-inf, -1, 0).
+// lp = the pick's log-probability over the sides that survive.
+__device__ __forceinline__ void ts_decide(float mt, int it, float st, float mx, int ix, float sx, int& tok, float& lp,
+                                          int& mass) {
+  const float lse_x = mx > -INFINITY ? mx + logf(sx) : -INFINITY;
+  mass = lse_x > mt ? 1 : 0;  // rule f: raw logits, the softmax normaliser is common to both sides
+  if (mass) {
+    tok = ix;
+    lp = -logf(sx);
+  } else {
+    float M = mt;
+    tok = it;
+    better_pair(M, tok, mx, ix);
+    const float a = mt > -INFINITY ? st * expf(mt - M) : 0.0f;
+    const float b = mx > -INFINITY ? sx * expf(mx - M) : 0.0f;
+    lp = -logf(a + b);
+  }
+  if (tok < 0) tok = 0;
+}
+
+// What the timestamp instantiation of the fused kernel takes beside the
+// scored form's arguments (unused, and never read, by the others).
+struct TsArgs {
+  const TsRule* rules;
+  int ts0;
+  float* xval;
+  int* xidx;
+  float* xsum;
+  int* out_mass;
+};
+
+// pick_from_lds of a timestamp decode: each workgroup leaves per row a text
+// candidate with its exp sum (pval / pidx / psum; workgroups that hold an id
+// below ts0) and a timestamp candidate with its own (xval / xidx / xsum;
+// workgroups that hold an id from ts0 on -- the workgroup ts0 falls in
+// leaves both), the same write-through stores ahead of the ticket; the
+// last-arriving workgroup merges each side, applies the mass rule and picks
+// (ts_decide).  f32 throughout; the longest chain of additions on the text
+// side is 16 per thread + 3 shuffles + ceil(ceil(ts0 / 128) / 8) candidates +
+// 3 shuffles, and one more to join the sides (73 at ts0 = 50365).
+__device__ __forceinline__ void pick_from_lds_ts(const float* lg, int B, int V, const TsArgs& ts,
+                                                 float* __restrict__ pval, int* __restrict__ pidx,
+                                                 float* __restrict__ psum, int* __restrict__ counter,
+                                                 int* __restrict__ out_tok, float* __restrict__ out_lp, int* ticket) {
+  const int tid = threadIdx.x, nwg = gridDim.x;
+  const int ts0 = ts.ts0;
+  const int nT = min(nwg, (ts0 + 127) / 128);  // workgroups [0, nT) hold text ids
+  const int jx0 = min(nwg, ts0 / 128);         // workgroups [jx0, nwg) hold timestamp ids
+  const bool has_t = (int)blockIdx.x < nT, has_x = (int)blockIdx.x >= jx0;
+  __syncthreads();
+  const int row = tid >> 3, part = tid & 7;
+  float tv = -INFINITY, xv = -INFINITY;
+  int ti = -1, xi = -1;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int c = part * 16 + j;
+    const int idx = blockIdx.x * 128 + c;
+    const float v = lg[row * kLgPickLd + c];
+    if (idx < V) {
+      if (idx < ts0)
+        better_pair(tv, ti, v, idx);
+      else
+        better_pair(xv, xi, v, idx);
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    const float v2 = __shfl_xor(tv, o, 64), v3 = __shfl_xor(xv, o, 64);
+    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
+    better_pair(tv, ti, v2, i2);
+    better_pair(xv, xi, v3, i3);
+  }
+  // each side's sum relative to its own maximum; a side with every logit masked: 0
+  float s_t = 0.0f, s_x = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int c = part * 16 + j;
+    const int idx = blockIdx.x * 128 + c;
+    const float v = lg[row * kLgPickLd + c];
+    if (idx < V) {
+      if (idx < ts0) {
+        if (tv > -INFINITY) s_t += expf(v - tv);
+      } else {
+        if (xv > -INFINITY) s_x += expf(v - xv);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    s_t += __shfl_xor(s_t, o, 64);
+    s_x += __shfl_xor(s_x, o, 64);
+  }
+  const uint32_t bytes = 32 * nwg * 4;
+  const __amdgpu_buffer_rsrc_t rtv = __builtin_amdgcn_make_buffer_rsrc(pval, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rti = __builtin_amdgcn_make_buffer_rsrc(pidx, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rts = __builtin_amdgcn_make_buffer_rsrc(psum, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxv = __builtin_amdgcn_make_buffer_rsrc(ts.xval, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxi = __builtin_amdgcn_make_buffer_rsrc(ts.xidx, 0, bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rxs = __builtin_amdgcn_make_buffer_rsrc(ts.xsum, 0, bytes, 0x00020000);
+  if (part == 0 && row < B) {
+    const uint32_t off = (uint32_t)(row * nwg + blockIdx.x) * 4;  // < bytes: row < 32, blockIdx.x < nwg
+    if (has_t) {
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, tv), rtv, off, 0, 16);  // sc1
+      __builtin_amdgcn_raw_buffer_store_b32((uint32_t)ti, rti, off, 0, 16);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s_t), rts, off, 0, 16);
+    }
+    if (has_x) {
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, xv), rxv, off, 0, 16);
+      __builtin_amdgcn_raw_buffer_store_b32((uint32_t)xi, rxi, off, 0, 16);
+      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s_x), rxs, off, 0, 16);
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    typedef __attribute__((address_space(1))) int gint;
+    const int prev = __hip_atomic_fetch_add((gint*)counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *ticket = prev == nwg - 1;
+  }
+  __syncthreads();
+  if (!*ticket) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler-only: loads stay below the ticket
+  tv = xv = -INFINITY;
+  ti = xi = -1;
+  if (row < B) {
+    for (int j = part; j < nT; j += 8) {
+      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+      const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rtv, off, 0, 16));
+      const int i = (int)__builtin_amdgcn_raw_buffer_load_b32(rti, off, 0, 16);
+      better_pair(tv, ti, v, i);
+    }
+    for (int j = jx0 + part; j < nwg; j += 8) {
+      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+      const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxv, off, 0, 16));
+      const int i = (int)__builtin_amdgcn_raw_buffer_load_b32(rxi, off, 0, 16);
+      better_pair(xv, xi, v, i);
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    const float v2 = __shfl_xor(tv, o, 64), v3 = __shfl_xor(xv, o, 64);
+    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
+    better_pair(tv, ti, v2, i2);
+    better_pair(xv, xi, v3, i3);
+  }
+  // tv = M_text, xv = M_ts in the row's 8 threads: the candidates again, rescaled to them
+  float S_t = 0.0f, S_x = 0.0f;
+  if (row < B) {
+    if (tv > -INFINITY)
+      for (int j = part; j < nT; j += 8) {
+        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+        const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rtv, off, 0, 16));
+        const float s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rts, off, 0, 16));
+        S_t += s * expf(v - tv);
+      }
+    if (xv > -INFINITY)
+      for (int j = jx0 + part; j < nwg; j += 8) {
+        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+        const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxv, off, 0, 16));
+        const float s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxs, off, 0, 16));
+        S_x += s * expf(v - xv);
+      }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    S_t += __shfl_xor(S_t, o, 64);
+    S_x += __shfl_xor(S_x, o, 64);
+  }
+  if (part == 0 && row < B) {
+    int tok, mass;
+    float lp;
+    ts_decide(tv, ti, S_t, xv, xi, S_x, tok, lp, mass);
+    out_tok[row] = tok;
+    out_lp[row] = lp;
+    if (ts.out_mass) ts.out_mass[row] = mass;
+  }
+  if (tid == 0) {
+    typedef __attribute__((address_space(1))) int gint;
+    __hip_atomic_store((gint*)counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+  }
+}
+
 constexpr int kLg2Chunk = 128;
 // 16-row groups of the fragment-tiled table (V padded to 128-row workgroups)
 __host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 127) / 128 * 8; }
@@ -1153,12 +1385,15 @@ __host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 12
 // (diagnostics, null in the product graph): the logits of
 // trace_ids[clip][step + 1][0..trace_k) are written to the same slots of
 // trace_out, as the pick sees them (EOT already masked).
-template <int NS, int SCORE = 0>
+// TS = 1 (timestamp transcribes): the masks of the rows' rule records
+// (ts_masked) while lg[] is written, and pick_from_lds_ts; `ts` is read by
+// that instantiation only.
+template <int NS, int SCORE = 0, int TS = 0>
 __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
     const _Float16* __restrict__ htiled, int B, int D, const _Float16* __restrict__ emb2, int V, int min_tokens,
     const DecodeState* __restrict__ state, float* __restrict__ pval, int* __restrict__ pidx, int* __restrict__ counter,
     int* __restrict__ out_tok, const int* __restrict__ trace_ids, float* __restrict__ trace_out, int trace_s1,
-    int trace_k, int* __restrict__ range_flag, float* __restrict__ psum, float* __restrict__ out_lp) {
+    int trace_k, int* __restrict__ range_flag, float* __restrict__ psum, float* __restrict__ out_lp, TsArgs ts) {
   constexpr int KS = kLg2Chunk / 32;             // Q4-block-sized k-steps per chunk
   constexpr int HCH = KS * 2 * NS * 1024;        // bytes of hidden fragments per chunk
   static_assert(HCH % (256 * 16) == 0, "whole glds rounds");
@@ -1255,6 +1490,12 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
   // acc[mt][nt]: lane holds clip 16 nt + l16, vocab v0 + 16 mt + 4 lq + j
   const int suppress = state->step + 1 < min_tokens;
   bool bad = false;
+  int4 rule[2] = {};  // TS: the records of this lane's two clips (a padded clip reads the last one's)
+  if constexpr (TS) {
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+      rule[nt] = *reinterpret_cast<const int4*>(ts.rules + min(16 * nt + l16, B - 1));
+  }
 #pragma unroll
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -1265,7 +1506,11 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
         const int n = v0 + vl;
         float v = acc[mt][nt][j] * kLgInv;
         bad |= n < V && 16 * nt + l16 < B && !__builtin_isfinite(v);
-        if (n >= V || (suppress && n == kEOT)) v = -INFINITY;
+        if constexpr (TS) {
+          if (n >= V || ts_masked(n, ts.ts0, rule[nt], suppress != 0)) v = -INFINITY;
+        } else {
+          if (n >= V || (suppress && n == kEOT)) v = -INFINITY;
+        }
         lg[(16 * nt + l16) * kLgPickLd + wave * 32 + vl] = v;
       }
   // an MFMA operand out of the f16-pair range upstream turns every logit of
@@ -1282,7 +1527,10 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
         if (id >= 0 && id < 128) trace_out[o] = lg[b * kLgPickLd + id];
       }
   }
-  pick_from_lds<SCORE>(lg, B, V, pval, pidx, psum, counter, out_tok, out_lp, ticket);
+  if constexpr (TS)
+    pick_from_lds_ts(lg, B, V, ts, pval, pidx, psum, counter, out_tok, out_lp, ticket);
+  else
+    pick_from_lds<SCORE>(lg, B, V, pval, pidx, psum, counter, out_tok, out_lp, ticket);
 }
 
 int logits_argmax_groups(int V) { return (V + 127) / 128; }
@@ -1340,11 +1588,11 @@ hipError_t launch_logits_argmax(const _Float16* htiled, int B, int D, const _Flo
   if (ns == 2)
     hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 0>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
                        min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, none, none);
+                       range_flag, none, none, TsArgs{});
   else
     hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 0>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
                        min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, none, none);
+                       range_flag, none, none, TsArgs{});
   return hipGetLastError();
 }
 
@@ -1358,11 +1606,11 @@ hipError_t launch_logits_argmax_scored(const _Float16* htiled, int B, int D, con
   if (ns == 2)
     hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
                        min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, psum, out_lp);
+                       range_flag, psum, out_lp, TsArgs{});
   else
     hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
                        min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, psum, out_lp);
+                       range_flag, psum, out_lp, TsArgs{});
   return hipGetLastError();
 }
 
@@ -1512,6 +1760,162 @@ __global__ void gather_int_kernel(const int* __restrict__ src, int stride, int* 
 
 hipError_t launch_gather_int(const int* src, int stride, int* dst, int n, hipStream_t st) {
   hipLaunchKernelGGL(gather_int_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, stride, dst, n);
+  return hipGetLastError();
+}
+
+// ----------------------------------------- timestamp decoding, launches --
+// Kept behind every other kernel of this file: the fused kernel's TS
+// instantiations, the row kernel and the bookkeeping kernel are emitted after
+// the kernels that were here before them, which keep their places in the code
+// object.
+hipError_t launch_logits_argmax_ts(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
+                                   int min_tokens, const DecodeState* state, const TsRule* rules, int ts0,
+                                   float* pval, int* pidx, float* psum, float* xval, int* xidx, float* xsum,
+                                   int* counter, int* out_tok, float* out_lp, int* out_mass, const int* trace_ids,
+                                   float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st) {
+  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled || !psum || !out_lp || !rules ||
+      !xval || !xidx || !xsum || ts0 < 1)
+    return hipErrorInvalidValue;
+  const dim3 grid(logits_argmax_groups(V));
+  const TsArgs ts{rules, ts0, xval, xidx, xsum, out_mass};
+  if (ns == 2)
+    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
+                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
+                       range_flag, psum, out_lp, ts);
+  else
+    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
+                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
+                       range_flag, psum, out_lp, ts);
+  return hipGetLastError();
+}
+
+// -------------------------------------------- timestamp pick of a row --
+// The timestamp rule over a stored logit row (the prompt's pick, decode
+// groups wider than 32 rows): one workgroup per row, two passes -- each
+// side's (max, index) under ts_masked, then each side's sum exp(z - max) --
+// and ts_decide in thread 0.  Per side a thread adds ceil(V / 256) terms, 6
+// shuffle adds, 3 adds over the waves.
+__global__ __launch_bounds__(256) void row_timestamp_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                            int suppress_fixed, int min_tokens,
+                                                            const DecodeState* __restrict__ state,
+                                                            const TsRule* __restrict__ rules, int ts0,
+                                                            int* __restrict__ out_tok, float* __restrict__ out_lp,
+                                                            int* __restrict__ out_mass, int* __restrict__ range_flag) {
+  __shared__ float sv[2][4], ss[2][4];
+  __shared__ int si[2][4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* z = logits + (size_t)b * ld;
+  const bool suppress = state ? (state->step + 1 < min_tokens) : suppress_fixed != 0;
+  const int4 rule = *reinterpret_cast<const int4*>(rules + b);
+  float tv = -INFINITY, xv = -INFINITY;
+  int ti = -1, xi = -1;
+  bool bad = false;
+  for (int i = tid; i < V; i += 256) {
+    float v = z[i];
+    bad |= !__builtin_isfinite(v);
+    if (ts_masked(i, ts0, rule, suppress)) v = -INFINITY;
+    if (i < ts0)
+      better(tv, ti, v, i);
+    else
+      better(xv, xi, v, i);
+  }
+  if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float v2 = __shfl_xor(tv, o, 64), v3 = __shfl_xor(xv, o, 64);
+    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
+    better(tv, ti, v2, i2);
+    better(xv, xi, v3, i3);
+  }
+  if (lane == 0) {
+    sv[0][wave] = tv;
+    si[0][wave] = ti;
+    sv[1][wave] = xv;
+    si[1][wave] = xi;
+  }
+  __syncthreads();
+  tv = xv = -INFINITY;
+  ti = xi = -1;
+  for (int w = 0; w < 4; ++w) {
+    better(tv, ti, sv[0][w], si[0][w]);
+    better(xv, xi, sv[1][w], si[1][w]);
+  }
+  float s_t = 0.0f, s_x = 0.0f;
+  for (int i = tid; i < V; i += 256) {
+    const float v = ts_masked(i, ts0, rule, suppress) ? -INFINITY : z[i];
+    if (i < ts0) {
+      if (tv > -INFINITY) s_t += expf(v - tv);
+    } else {
+      if (xv > -INFINITY) s_x += expf(v - xv);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s_t += __shfl_xor(s_t, o, 64);
+    s_x += __shfl_xor(s_x, o, 64);
+  }
+  if (lane == 0) {
+    ss[0][wave] = s_t;
+    ss[1][wave] = s_x;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    s_t = ((ss[0][0] + ss[0][1]) + ss[0][2]) + ss[0][3];
+    s_x = ((ss[1][0] + ss[1][1]) + ss[1][2]) + ss[1][3];
+    int tok, mass;
+    float lp;
+    ts_decide(tv, ti, s_t, xv, xi, s_x, tok, lp, mass);
+    out_tok[b] = tok;
+    if (out_lp) out_lp[b] = lp;
+    if (out_mass) out_mass[b] = mass;
+  }
+}
+
+hipError_t launch_row_timestamp(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
+                                const DecodeState* state, const TsRule* rules, int ts0, int* out_tok, float* out_lp,
+                                int* out_mass, int* range_flag, hipStream_t st) {
+  if (rows < 1 || V < 1 || V > ld || !logits || !rules || !out_tok || ts0 < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(row_timestamp_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, suppress_eot, min_tokens,
+                     state, rules, ts0, out_tok, out_lp, out_mass, range_flag);
+  return hipGetLastError();
+}
+
+// bookkeep_scored_kernel of a timestamp transcribe: every row's rule record
+// also advances by the token that is fed to this step (ts_rule_step), done
+// clips included -- their picks go nowhere, and a record of any history leaves
+// a non-empty allowed set.
+__global__ void bookkeep_ts_kernel(const int* __restrict__ next, const float* __restrict__ next_lp,
+                                   int* __restrict__ tokens, float* __restrict__ logprob, int* __restrict__ ntok,
+                                   int* __restrict__ done, int B, int max_tokens, int eot_stop, DecodeState* state,
+                                   TsRule* __restrict__ rules, int ts0, int V) {
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const int tk = next[b];
+    if (!done[b]) {
+      const float lp = next_lp[b];
+      if (eot_stop && tk == kEOT) {
+        done[b] = 1;
+        atomicAdd(&state->n_done, 1);
+        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
+      } else if (ntok[b] < max_tokens) {
+        tokens[(size_t)b * max_tokens + ntok[b]] = tk;
+        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
+        ntok[b] += 1;
+      }
+    }
+    rules[b] = ts_rule_step(rules[b], tk, ts0, V);
+  }
+  if (threadIdx.x == 0) {
+    state->position += 1;
+    state->kv_len += 1;
+    state->step += 1;
+  }
+}
+
+hipError_t launch_bookkeep_ts(const int* next_tok, const float* next_lp, int* tokens, float* logprob, int* n_tokens,
+                              int* done, int B, int max_tokens, int eot_stop, DecodeState* state, TsRule* rules,
+                              int ts0, int V, hipStream_t st) {
+  hipLaunchKernelGGL(bookkeep_ts_kernel, dim3(1), dim3(256), 0, st, next_tok, next_lp, tokens, logprob, n_tokens, done,
+                     B, max_tokens, eot_stop, state, rules, ts0, V);
   return hipGetLastError();
 }
 

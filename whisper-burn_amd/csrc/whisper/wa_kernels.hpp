@@ -199,4 +199,51 @@ hipError_t launch_bookkeep_scored(const int* next_tok, const float* next_lp, int
 hipError_t launch_argmax_step(const float* logits, int B, int V, int min_tokens, const DecodeState* state,
                               int* out_tok, int* range_flag, hipStream_t st);
 
+// ---- timestamp decoding (wa_transcribe_timestamps) ----------------------
+// OpenAI Whisper's ApplyTimestampRules, per row, as a record the bookkeeping
+// kernel keeps on the device (ts0 = no_timestamps + 1, the id of <|0.00|>):
+//   history (what the sampled tokens s so far decide)
+//     last    s[-1] is a timestamp            penult  len(s) < 2 or s[-2] is one
+//     t_last  the last timestamp in s, -1: none      first   len(s) == 0
+//   masks derived from it, read by the pick kernels (ts_masked, wa_kernels.hip)
+//     ids >= ts0        allowed inside [ts_lo, ts_hi] only
+//     ids in (EOT, ts0) never (the specials)
+//     EOT               unless first, or the step suppresses it (whisper.rs:97-98, 120-122)
+//     ids < EOT         when text_ok
+// The allowed set is never empty: the first pick keeps [ts0, ts_hi] with
+// ts_hi >= ts0; after two timestamps (or one as the only token) every text id
+// stays; after text + timestamp [t_last, V) stays and t_last <= V - 1;
+// otherwise every text id stays.
+struct TsRule {
+  int text_ok, ts_lo, ts_hi, first;
+  int last, penult, t_last, pad;
+};
+// The record of an empty history: max_initial < 0 leaves the first timestamp unbounded.
+TsRule ts_rule_first(int ts0, int V, int max_initial);
+// The record after `tok` is appended to the history `r` describes.
+TsRule ts_rule_next(const TsRule& r, int tok, int ts0, int V);
+
+// The timestamp form of launch_logits_argmax_scored: masks a-e of the rule
+// applied while the logits are written, then the mass rule (the timestamps'
+// logsumexp against the best text logit) and the pick in the last-arriving
+// workgroup.  pval / pidx / psum carry the text side (ids < ts0), xval / xidx
+// / xsum (three more 32 * logits_argmax_groups(V) arrays) the timestamp side.
+// out_lp[b]: the pick's log-probability over the finally masked row.
+// out_mass (nullable): 1 where the mass rule masked the text side of row b.
+hipError_t launch_logits_argmax_ts(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
+                                   int min_tokens, const DecodeState* state, const TsRule* rules, int ts0,
+                                   float* pval, int* pidx, float* psum, float* xval, int* xidx, float* xsum,
+                                   int* counter, int* out_tok, float* out_lp, int* out_mass, const int* trace_ids,
+                                   float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st);
+// The same rule over stored logit rows [rows][ld] (the prompt's pick, decode
+// groups wider than 32 rows): EOT suppressed when suppress_eot != 0 or, state
+// non-null, when state->step + 1 < min_tokens.
+hipError_t launch_row_timestamp(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
+                                const DecodeState* state, const TsRule* rules, int ts0, int* out_tok, float* out_lp,
+                                int* out_mass, int* range_flag, hipStream_t st);
+// launch_bookkeep_scored that also advances every row's rule record by its next token.
+hipError_t launch_bookkeep_ts(const int* next_tok, const float* next_lp, int* tokens, float* logprob, int* n_tokens,
+                              int* done, int B, int max_tokens, int eot_stop, DecodeState* state, TsRule* rules,
+                              int ts0, int V, hipStream_t st);
+
 }  // namespace wa

@@ -152,12 +152,19 @@ struct DecGroup {
   float *next_lp = nullptr, *logprob = nullptr, *lg_sum = nullptr;
   float *no_speech = nullptr, *lang_prob = nullptr, *z0 = nullptr;
   int* lang_tok = nullptr;
+  // timestamp transcribes (wa_transcribe_timestamps; allocated by the first
+  // one, ensure_ts_buffers): every clip's rule record, advanced by the
+  // bookkeeping kernel, and the fused kernel's timestamp-side candidates,
+  // indices and sums [32][groups] beside lg_val / lg_idx / lg_sum
+  TsRule* ts_rules = nullptr;
+  float *lg_xval = nullptr, *lg_xsum = nullptr;
+  int* lg_xidx = nullptr;
   DecodeState* state;
   void* ffn_ws = nullptr;  // range tier 2: wq4_ffn_forward_ws workspace (4 * nb rows)
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (scoring, lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
+  int64_t graph_key = -1;  // (timestamps, scoring, lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
   // graphs of other layouts this group ran (ensure_graph): a call of units of
   // three and two, with and without the masked stream beside them, goes
   // through four keys per group and comes back to each
@@ -259,6 +266,14 @@ struct wa_model {
   // probability in the groups' score buffers
   bool score = false;
   bool score_alloc_ok = false;  // every group's score buffers allocated (ensure_score_buffers)
+  // a timestamp transcribe is running (wa_transcribe_timestamps /
+  // wa_transcribe_batches_timestamps; `score` is set with it): the prompt
+  // drops NO_TIMESTAMPS and every pick runs under the timestamp rules, the
+  // first timestamp at most ts_max_initial ids past <|0.00|> (< 0: unbounded)
+  bool ts = false;
+  int ts_max_initial = 50;
+  bool ts_alloc_ok = false;  // every group's timestamp buffers allocated (ensure_ts_buffers)
+  int ts0() const { return cfg.no_timestamps_token() + 1; }  // <|0.00|>
   // live kernel timing (wa_profile_*)
   struct Pending {
     hipEvent_t a, b;
@@ -327,6 +342,7 @@ void kv_config(wa_model* m, int max_batch);
 wq4_status alloc_activations(wa_model* m);
 wq4_status ensure_ffn_ws(wa_model* m);
 wq4_status ensure_score_buffers(wa_model* m);
+wq4_status ensure_ts_buffers(wa_model* m);
 int decode_groups(int B);
 wq4_status encoder_front(wa_model* m, const float* mel, int B, hipStream_t st);
 wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);

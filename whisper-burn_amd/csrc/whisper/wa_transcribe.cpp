@@ -553,6 +553,21 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
 
 }  // namespace
 
+// The timestamp mode around a transcribe: the score and timestamp buffers,
+// then m->ts (and m->score: a timestamp pick always leaves its
+// log-probability) for the length of `run`.
+template <class Run>
+static wq4_status with_timestamps(wa_model* m, int max_initial, Run run) {
+  WA_HIP(hipSetDevice(m->device));
+  WA_TRY(ensure_score_buffers(m));
+  WA_TRY(ensure_ts_buffers(m));
+  m->score = m->ts = true;
+  m->ts_max_initial = max_initial;
+  const wq4_status s = run();
+  m->score = m->ts = false;
+  return s;
+}
+
 extern "C" {
 
 // wa_transcribe, and wa_transcribe_scored with its scores: the scores are
@@ -661,6 +676,72 @@ wq4_status wa_transcribe_batches_scored(wa_model* m, const float* mel_dev, int n
                                           tokens_out, n_tokens_out, stream, scores);
   m->score = false;
   return s;
+}
+
+wq4_status wa_transcribe_timestamps(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                    int eot_stop, int max_initial, int32_t* tokens_out, int32_t* n_tokens_out,
+                                    const wa_scores* scores, void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  return with_timestamps(m, max_initial, [&] {
+    return transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
+                            scores);
+  });
+}
+
+wq4_status wa_transcribe_batches_timestamps(wa_model* m, const float* mel_dev, int n_batches, int n_clips,
+                                            int lang_token, int max_tokens, int eot_stop, int max_initial,
+                                            int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
+                                            void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  return with_timestamps(m, max_initial, [&] {
+    return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
+                              n_tokens_out, stream, scores);
+  });
+}
+
+// OpenAI transcribe.py's slicing of one window's tokens at consecutive
+// timestamp pairs (host only).
+wq4_status wa_segments_from_tokens(const int32_t* tokens, int n, int ts0, wa_segment* segs, int cap, int* n_segs,
+                                   int* seek_frames) {
+  if (!n_segs || !seek_frames || n < 0 || cap < 0 || (n > 0 && !tokens) || (cap > 0 && !segs))
+    return fail(WQ4_EINVAL, "bad arguments");
+  std::vector<wa_segment> out;
+  int seek = 3000;
+  auto is_ts = [&](int i) { return tokens[i] >= ts0; };
+  auto secs = [&](int i) { return (float)((tokens[i] - ts0) * 0.02); };
+  if (n > 0) {
+    const bool single_end = n >= 2 && !is_ts(n - 2) && is_ts(n - 1);
+    std::vector<int> cuts;
+    for (int i = 1; i < n; ++i)
+      if (is_ts(i - 1) && is_ts(i)) cuts.push_back(i);
+    if (!cuts.empty()) {
+      if (single_end) cuts.push_back(n);
+      int last = 0;
+      for (int c : cuts) {
+        out.push_back(wa_segment{secs(last), secs(c - 1), last, c});
+        last = c;
+      }
+      if (!single_end) seek = (tokens[last - 1] - ts0) * 2;
+    } else {
+      float end = 30.0f;
+      for (int i = n - 1; i >= 0; --i)
+        if (is_ts(i)) {  // the last timestamp, when it is not <|0.00|>
+          if (tokens[i] != ts0) end = secs(i);
+          break;
+        }
+      out.push_back(wa_segment{0.0f, end, 0, n});
+    }
+  }
+  *n_segs = (int)out.size();
+  *seek_frames = seek;
+  if ((int)out.size() > cap) return fail(WQ4_EINVAL, "segs too small: *n_segs segments are needed");
+  std::copy(out.begin(), out.end(), segs);
+  return WQ4_OK;
 }
 
 wq4_status wa_last_pipeline_stats(const wa_model* m, float* out) {

@@ -29,6 +29,16 @@ class Scores(ctypes.Structure):
                 ("lang_token", ctypes.POINTER(ctypes.c_int32)), ("lang_prob", ctypes.POINTER(ctypes.c_float))]
 
 
+class Segment(ctypes.Structure):
+    """struct wa_segment: tokens [tok_begin, tok_end) from start_s to end_s."""
+
+    _fields_ = [("start_s", ctypes.c_float), ("end_s", ctypes.c_float), ("tok_begin", ctypes.c_int32),
+                ("tok_end", ctypes.c_int32)]
+
+
+RULE_FIELDS = ("text_ok", "ts_lo", "ts_hi", "first", "last", "penult", "t_last", "pad")  # a rule record's 8 int32
+
+
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
@@ -107,6 +117,20 @@ def lib() -> ctypes.CDLL:
         L.wa_row_logprob_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp]
         for n in ("wa_transcribe_scored", "wa_transcribe_batches_scored", "wa_logits_logprob_check",
                   "wa_row_logprob_check"):
+            getattr(L, n).restype = c_int
+        L.wa_transcribe_timestamps.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
+        L.wa_transcribe_batches_timestamps.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, i32p, i32p,
+                                                       sp, vp]
+        L.wa_segments_from_tokens.argtypes = [i32p, c_int, c_int, ctypes.POINTER(Segment), c_int,
+                                              ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+        L.wa_timestamp_rule.argtypes = [i32p, c_int, c_int, c_int, c_int, i32p]
+        L.wa_logits_timestamp_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, i32p, vp, vp,
+                                                vp, vp]
+        L.wa_row_timestamp_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, i32p, vp, vp, vp]
+        L.wa_timestamp_bookkeep_check.argtypes = [c_int, i32p, c_int, c_int, c_int, c_int, c_int, i32p]
+        for n in ("wa_transcribe_timestamps", "wa_transcribe_batches_timestamps", "wa_segments_from_tokens",
+                  "wa_timestamp_rule", "wa_logits_timestamp_check", "wa_row_timestamp_check",
+                  "wa_timestamp_bookkeep_check"):
             getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
@@ -327,6 +351,89 @@ def row_logprob_check(logits, lo: int, hi: int, mask_eot: bool = False, idx=None
     return out
 
 
+def segments_from_tokens(tokens, ts0: int = 50365, cap: Optional[int] = None):
+    """The segments of one 30-s window's tokens (wa_segments_from_tokens; host
+    only): ([(start_s, end_s, tokens of the segment)], seek_frames).  ts0 is
+    <|0.00|>: 50365 for Large-V3 / TINY_TEST, 50364 for Medium.  cap: room
+    for that many segments (default: enough); too small raises WQ4Error."""
+    toks = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+    n = int(toks.size)
+    room = max(1, n) if cap is None else int(cap)
+    segs = (Segment * max(1, room))()
+    ns, seek = ctypes.c_int(), ctypes.c_int()
+    check(lib().wa_segments_from_tokens(toks.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n, int(ts0), segs, room,
+                                        ctypes.byref(ns), ctypes.byref(seek)))
+    out = [(float(segs[i].start_s), float(segs[i].end_s), toks[segs[i].tok_begin:segs[i].tok_end].tolist())
+           for i in range(ns.value)]
+    return out, int(seek.value)
+
+
+def timestamp_rule(tokens, ts0: int, V: int, max_initial: int = 50) -> np.ndarray:
+    """The rule record (8 int32, RULE_FIELDS) after one clip's sampled tokens
+    (wa_timestamp_rule; host only)."""
+    toks = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+    rec = np.zeros(8, np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    check(lib().wa_timestamp_rule(toks.ctypes.data_as(i32p), int(toks.size), int(ts0), int(V), int(max_initial),
+                                  rec.ctypes.data_as(i32p)))
+    return rec
+
+
+def _records(histories, ts0: int, V: int, max_initial: int) -> np.ndarray:
+    return np.ascontiguousarray(np.stack([timestamp_rule(h, ts0, V, max_initial) for h in histories]), np.int32)
+
+
+def logits_timestamp_check(hid, emb, histories, step: int, ts0: int, max_initial: int = 50,
+                           precision: int = wq4.PREC_F16X2, logprob=None):
+    """The timestamp form of the fused logits + pick (wa_logits_timestamp_check):
+    hid cuda f32 [B, D], emb cuda f32 [V, D], histories = each row's sampled
+    tokens so far -> (tokens int32 [B], logprob f32, logits [B, V] as the pick
+    saw them: masks a-e from the kernel, rule f's mask of [0, ts0) applied
+    here where the kernel reports it, mass int32 [B])."""
+    torch = _torch()
+    B, D = hid.shape
+    V = emb.shape[0]
+    rec = _records(histories, ts0, V, max_initial)
+    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
+    mass = torch.empty(B, device=hid.device, dtype=torch.int32)
+    lp = torch.empty(B, device=hid.device, dtype=torch.float32) if logprob is None else logprob
+    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32)
+    check(lib().wa_logits_timestamp_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
+                                          precision, ts0, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                          _ptr(tok), _ptr(lp), _ptr(mass), _ptr(lg)))
+    lg[mass.bool(), :ts0] = float("-inf")
+    return tok, lp, lg, mass
+
+
+def row_timestamp_check(logits, histories, ts0: int, suppress_eot: bool = False, max_initial: int = 50):
+    """The stored-logits kernel of the timestamp rule (wa_row_timestamp_check):
+    logits cuda f32 [R, V] -> (tokens int32 [R], logprob f32 [R], mass int32 [R])."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    rec = _records(histories, ts0, V, max_initial)
+    tok = torch.empty(R, device=logits.device, dtype=torch.int32)
+    mass = torch.empty(R, device=logits.device, dtype=torch.int32)
+    lp = torch.empty(R, device=logits.device, dtype=torch.float32)
+    check(lib().wa_row_timestamp_check(_dev(logits), _ptr(logits), R, V, 1 if suppress_eot else 0, ts0,
+                                       rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(tok), _ptr(lp),
+                                       _ptr(mass)))
+    return tok, lp, mass
+
+
+def timestamp_bookkeep_check(tokens, ts0: int, V: int, max_initial: int = 50, device: int = 0) -> np.ndarray:
+    """Token sequences int32 [R, S] through the timestamp bookkeeping kernel,
+    one token per row and launch (wa_timestamp_bookkeep_check) -> the rule
+    records after each launch, int32 [S, R, 8]."""
+    toks = np.ascontiguousarray(tokens, np.int32)
+    R, S = toks.shape
+    out = np.zeros((S, R, 8), np.int32)
+    i32p = ctypes.POINTER(ctypes.c_int32)
+    check(lib().wa_timestamp_bookkeep_check(device, toks.ctypes.data_as(i32p), R, S, int(ts0), int(V),
+                                            int(max_initial), out.ctypes.data_as(i32p)))
+    return out
+
+
 def _scored_clip(toks, n, lp, ns, lt, lpr) -> dict:
     """One clip of a scored transcribe: lp its max_tokens + 1 log-probability slots."""
     n = int(n)
@@ -465,7 +572,36 @@ class WhisperModel:
                                           self._stream()))
         return [[toks[i, b, : nt[i, b]].tolist() for b in range(B)] for i in range(NB)]
 
-    def _scored(self, mels, NB: Optional[int], lang_token, max_tokens: int, eot_stop: bool):
+    @property
+    def timestamp_begin(self) -> int:
+        """<|0.00|>, the id after NO_TIMESTAMPS (50365 for Large-V3 / TINY_TEST, 50364 for Medium)."""
+        return 50260 + self.config["n_lang"] + 4 + 1
+
+    def _timestamped(self, clips):
+        for c in clips:
+            c["segments"], c["seek_frames"] = segments_from_tokens(c["tokens"], self.timestamp_begin)
+        return clips
+
+    def transcribe_timestamps(self, mel, lang_token: Optional[int] = 50259, max_tokens: int = 224,
+                              eot_stop: bool = True, max_initial: int = 50) -> list[dict]:
+        """transcribe with timestamp tokens (wa_transcribe_timestamps): the prompt
+        without NO_TIMESTAMPS, every pick under OpenAI's timestamp rules.  Per
+        clip the dict of transcribe_scored (tokens: text and timestamp ids
+        interleaved; the scores over the masked rows) plus segments, a list of
+        (start_s, end_s, tokens), and seek_frames, the mel frame a following
+        window would start at (segments_from_tokens)."""
+        return self._timestamped(self._scored(mel, None, lang_token, max_tokens, eot_stop, max_initial))
+
+    def transcribe_batches_timestamps(self, mels, lang_token: Optional[int] = 50259, max_tokens: int = 224,
+                                      eot_stop: bool = True, max_initial: int = 50) -> list[list[dict]]:
+        """transcribe_batches with timestamp tokens (wa_transcribe_batches_timestamps):
+        mels cuda f32 [NB, B, n_mels, 3000] -> NB lists of B dicts as transcribe_timestamps."""
+        assert mels.dim() == 4
+        return [self._timestamped(b)
+                for b in self._scored(mels, mels.shape[0], lang_token, max_tokens, eot_stop, max_initial)]
+
+    def _scored(self, mels, NB: Optional[int], lang_token, max_tokens: int, eot_stop: bool,
+                max_initial: Optional[int] = None):
         torch = _torch()
         mels = mels.contiguous()
         assert mels.dtype == torch.float32 and mels.is_cuda
@@ -479,7 +615,12 @@ class WhisperModel:
         sc = Scores(lp.ctypes.data_as(f32p), ns.ctypes.data_as(f32p), lt.ctypes.data_as(i32p),
                     lpr.ctypes.data_as(f32p))
         lang = -1 if lang_token is None else int(lang_token)
-        if NB is None:
+        if max_initial is not None:  # the timestamp entries: max_initial before the outputs
+            f = lib().wa_transcribe_timestamps if NB is None else lib().wa_transcribe_batches_timestamps
+            head = (self._h, _ptr(mels)) + ((B,) if NB is None else (NB, B))
+            check(f(*head, lang, max_tokens, 1 if eot_stop else 0, int(max_initial), toks.ctypes.data_as(i32p),
+                    nt.ctypes.data_as(i32p), ctypes.byref(sc), self._stream()))
+        elif NB is None:
             check(lib().wa_transcribe_scored(self._h, _ptr(mels), B, lang, max_tokens, 1 if eot_stop else 0,
                                              toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), ctypes.byref(sc),
                                              self._stream()))
