@@ -1,5 +1,6 @@
 // wa_checks.cpp -- C ABI entries that run one kernel on caller-supplied
 // buffers (the wa_*_check test entries) and the log-mel front-end.
+#include <cmath>
 #include <map>
 #include <mutex>
 
@@ -293,6 +294,91 @@ wq4_status wa_timestamp_bookkeep_check(int device, const int32_t* tokens, int n_
     WA_HIP(launch_bookkeep_ts(next, lp, toks, logprob, ntok, done, n_rows, kMaxTokens, 0, st, rules, ts0, V, nullptr));
     WA_HIP(hipMemcpy(records_out + (size_t)s * B * 8, rules, B * sizeof(TsRule), hipMemcpyDeviceToHost));
   }
+  return WQ4_OK;
+}
+
+// ---- temperature sampling: the product kernels on caller data -------------
+wq4_status wa_logits_sample_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                  int step, wq4_precision prec, const float* temperature, const uint64_t* seed,
+                                  int ts0, const int32_t* records, int32_t* tok_dev, float* logprob_dev,
+                                  int32_t* mass_dev, float* logits_dev) {
+  if (!hid_dev || !emb_dev || !tok_dev || !logprob_dev || !temperature || !seed)
+    return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > 32 || V < 1 || step < 0 || step > 16 || (records && ts0 < 1) ||
+      !emb_tiled_supported(D))
+    return fail(WQ4_EINVAL, "bad sizes");
+  for (int b = 0; b < n_clips; ++b)
+    if (!(temperature[b] >= 0.0f) || !std::isfinite(temperature[b]))
+      return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  const int ns = planes(prec);
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  const size_t tb = wq4_atiled_bytes(n_clips, D, prec);
+  auto* emb2 = d.alloc<_Float16>((size_t)emb_tiled_rows(V) * ns * D);
+  auto* st = d.alloc<DecodeState>(1);
+  auto* scr = d.alloc<float>((size_t)logits_sample_scratch_floats(V));
+  auto* ctr = d.alloc<int>(1);
+  auto* ht = d.alloc<_Float16>(tb / 2);
+  auto* temp = d.alloc<float>(n_clips);
+  auto* sd = d.alloc<uint64_t>(n_clips);
+  if (!emb2 || !st || !scr || !ctr || !ht || !temp || !sd) return fail(WQ4_ENOMEM, "allocation failed");
+  TsRule* rules = nullptr;
+  if (records) {
+    rules = d.alloc<TsRule>(n_clips);
+    if (!rules) return fail(WQ4_ENOMEM, "allocation failed");
+    WA_HIP(hipMemcpy(rules, records, (size_t)n_clips * sizeof(TsRule), hipMemcpyHostToDevice));
+  }
+  WA_HIP(hipMemcpy(temp, temperature, (size_t)n_clips * 4, hipMemcpyHostToDevice));
+  WA_HIP(hipMemcpy(sd, seed, (size_t)n_clips * 8, hipMemcpyHostToDevice));
+  WA_HIP(launch_emb_tiled(emb_dev, V, D, ns, emb2, nullptr));
+  WA_WQ4(wq4_tile_activations(hid_dev, n_clips, D, D, prec, ht, tb, nullptr));
+  // the state's step is the caller's (the pick index is step + 1); a trace
+  // writes slot step + 1 of [clip][step + 2][V], every id listed there
+  const DecodeState s0{0, 0, step, 0};
+  WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  WA_HIP(hipMemset(ctr, 0, sizeof(int)));
+  const int s1 = step + 2;
+  int* ids = nullptr;
+  float* tr = nullptr;
+  if (logits_dev) {
+    ids = d.alloc<int>((size_t)n_clips * s1 * V);
+    tr = d.alloc<float>((size_t)n_clips * s1 * V);
+    if (!ids || !tr) return fail(WQ4_ENOMEM, "allocation failed");
+    std::vector<int> h((size_t)n_clips * s1 * V, 0);
+    for (int b = 0; b < n_clips; ++b)
+      for (int v = 0; v < V; ++v) h[((size_t)b * s1 + step + 1) * V + v] = v;
+    WA_HIP(hipMemcpy(ids, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+  }
+  WA_HIP(launch_logits_argmax_sample(ht, n_clips, D, emb2, ns, V, kMinTokens, st, temp, sd, rules, ts0, scr, ctr,
+                                     tok_dev, logprob_dev, mass_dev, ids, tr, s1, V, nullptr, nullptr));
+  if (logits_dev)
+    for (int b = 0; b < n_clips; ++b)
+      WA_HIP(hipMemcpy(logits_dev + (size_t)b * V, tr + ((size_t)b * s1 + step + 1) * V, (size_t)V * 4,
+                       hipMemcpyDeviceToDevice));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+wq4_status wa_row_sample_check(int device, const float* logits_dev, int n_rows, int V, int suppress_eot, int pick,
+                               const float* temperature, const uint64_t* seed, int ts0, const int32_t* records,
+                               int32_t* tok_dev, float* logprob_dev, int32_t* mass_dev) {
+  if (!logits_dev || !tok_dev || !logprob_dev || !temperature || !seed) return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || n_rows > 32 || V < 1 || pick < 0 || (records && ts0 < 1)) return fail(WQ4_EINVAL, "bad sizes");
+  for (int b = 0; b < n_rows; ++b)
+    if (!(temperature[b] >= 0.0f) || !std::isfinite(temperature[b]))
+      return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  auto* temp = d.alloc<float>(n_rows);
+  auto* sd = d.alloc<uint64_t>(n_rows);
+  TsRule* rules = records ? d.alloc<TsRule>(n_rows) : nullptr;
+  if (!temp || !sd || (records && !rules)) return fail(WQ4_ENOMEM, "allocation failed");
+  if (records) WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
+  WA_HIP(hipMemcpy(temp, temperature, (size_t)n_rows * 4, hipMemcpyHostToDevice));
+  WA_HIP(hipMemcpy(sd, seed, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+  WA_HIP(launch_row_sample(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, temp, sd, pick, tok_dev,
+                           logprob_dev, mass_dev, nullptr, nullptr));
+  WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }
 

@@ -91,7 +91,11 @@ wq4_status decode_step(wa_model* m, DecGroup& g, int eot_stop, hipStream_t st) {
   else
     WA_HIP(launch_bookkeep(g.next_tok, g.tokens, g.ntok, g.done, g.nb, kMaxTokens, eot_stop, g.state, st));
   WA_TRY(decoder_forward(m, g, g.next_tok, 1, g.state, 0, 0, st));
-  if (!fused_pick(g, 1, g.state) && m->ts) {  // the timestamp rule over the stored rows
+  if (!fused_pick(g, 1, g.state) && m->sample) {  // the sampled pick over the stored rows, pick step + 1
+    WA_HIP(launch_row_sample(g.logits, g.nb, m->cfg.n_vocab, m->cfg.n_vocab, 0, kMinTokens, g.state,
+                             m->ts ? g.ts_rules : nullptr, m->ts0(), g.smp_temp, g.smp_seed, 0, g.next_tok, g.next_lp,
+                             nullptr, m->range_flag, st));
+  } else if (!fused_pick(g, 1, g.state) && m->ts) {  // the timestamp rule over the stored rows
     WA_HIP(launch_row_timestamp(g.logits, g.nb, m->cfg.n_vocab, m->cfg.n_vocab, 0, kMinTokens, g.state, g.ts_rules,
                                 m->ts0(), g.next_tok, g.next_lp, nullptr, m->range_flag, st));
   } else if (!fused_pick(g, 1, g.state)) {
@@ -446,7 +450,13 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
     // embedding planes' precision)
     WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, m->prec, g.hid_t, nullptr, st));
     const size_t tofs = (size_t)g.b0 * m->trace_s1 * m->trace_k;
-    if (m->ts)  // the TS instantiation: the rows' rule records applied, the pick and its log-probability
+    if (m->sample)  // the SAMPLE instantiations: the Gumbel-max pick at the rows' temperatures and seeds
+      WA_HIP(launch_logits_argmax_sample(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.smp_temp,
+                                         g.smp_seed, m->ts ? g.ts_rules : nullptr, m->ts0(), g.smp_scr, g.lg_ctr,
+                                         g.next_tok, g.next_lp, nullptr, m->trace_out ? m->trace_ids + tofs : nullptr,
+                                         m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
+                                         m->range_flag, st));
+    else if (m->ts)  // the TS instantiation: the rows' rule records applied, the pick and its log-probability
       WA_HIP(launch_logits_argmax_ts(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.ts_rules,
                                      m->ts0(), g.lg_val, g.lg_idx, g.lg_sum, g.lg_xval, g.lg_xidx, g.lg_xsum, g.lg_ctr,
                                      g.next_tok, g.next_lp, nullptr, m->trace_out ? m->trace_ids + tofs : nullptr,
@@ -546,7 +556,21 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
     pos0 = 1 + plen;
     kv0 = plen;
   }
-  if (m->ts) {
+  if (m->sample) {
+    // the clips' temperatures and seeds, then pick 0 through the sampled row
+    // kernel: under the first pick's rule record (timestamps) or with EOT
+    // suppressed (whisper.rs:97-99)
+    // (pageable: the copies are staged before the calls return)
+    WA_HIP(hipMemcpyAsync(g.smp_temp, m->smp_temp + g.clip0, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    WA_HIP(hipMemcpyAsync(g.smp_seed, m->smp_seed + g.clip0, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    if (m->ts) {
+      const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, m->ts_max_initial));
+      WA_HIP(hipMemcpyAsync(g.ts_rules, first.data(), (size_t)B * sizeof(TsRule), hipMemcpyHostToDevice, st));
+    }
+    WA_HIP(launch_row_sample(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, m->ts ? g.ts_rules : nullptr, m->ts0(),
+                             g.smp_temp, g.smp_seed, 0, g.next_tok, g.next_lp, nullptr, m->range_flag, st));
+    WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
+  } else if (m->ts) {
     // every clip's rule record back to the empty history, then the first pick
     // under it (rule e; EOT is masked with the text) and its log-probability
     const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, m->ts_max_initial));  // pageable: staged
@@ -562,10 +586,18 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
       WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
     }
   }
-  const DecodeState init{pos0 - 1, kv0 - 1, -1, 0};
+  // frozen clips start done, and counted: the loop stops once the live ones emitted EOT
+  std::vector<int> done0(B, 0);
+  int n_frozen = 0;
+  if (m->frozen)
+    for (int b = 0; b < B; ++b) n_frozen += done0[b] = m->frozen[g.clip0 + b] ? 1 : 0;
+  const DecodeState init{pos0 - 1, kv0 - 1, -1, n_frozen};
   WA_HIP(hipMemcpyAsync(g.state, &init, sizeof(init), hipMemcpyHostToDevice, st));
   WA_HIP(hipMemsetAsync(g.ntok, 0, (size_t)B * 4, st));
-  WA_HIP(hipMemsetAsync(g.done, 0, (size_t)B * 4, st));
+  if (n_frozen)
+    WA_HIP(hipMemcpyAsync(g.done, done0.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));  // pageable: staged
+  else
+    WA_HIP(hipMemsetAsync(g.done, 0, (size_t)B * 4, st));
   WA_HIP(hipMemsetAsync(g.tokens, 0, (size_t)B * kMaxTokens * 4, st));
   return WQ4_OK;
 }
@@ -583,7 +615,9 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
       // scoring, the top digit (above every lane): an unscored key is what it was
       (m->score ? (int64_t)kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0) +
       // timestamps, the digit above it: the rule's max_initial is in the records, not in the graph
-      (m->ts ? (int64_t)2 * kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0);
+      (m->ts ? (int64_t)2 * kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0) +
+      // sampling, the digit above that: temperatures and seeds are read from the group's arrays, not baked in
+      (m->sample ? (int64_t)4 * kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0);
   if (g.graph && g.graph_key == key) return WQ4_OK;
   // the other layouts' graphs are kept: a call goes from units of three to
   // pairs or a lone last batch, beside the masked stream and without it, and
@@ -729,6 +763,33 @@ wq4_status ensure_ts_buffers(wa_model* m) {
   }
   m->bytes += m->groups.size() * (B * sizeof(TsRule) + 3 * ng * 4);
   m->ts_alloc_ok = true;
+  return WQ4_OK;
+}
+
+// The sampling buffers of every decode group (DecGroup::smp_temp ..):
+// allocated by the first sampled transcribe, all or nothing, never released.
+wq4_status ensure_sample_buffers(wa_model* m) {
+  if (m->sample_alloc_ok) return WQ4_OK;
+  const size_t B = (size_t)m->bmax;
+  const size_t nscr = (size_t)logits_sample_scratch_floats(m->cfg.n_vocab);
+  bool ok = true;
+  for (DecGroup& g : m->groups) {
+    g.smp_temp = m->dev.alloc<float>(B);
+    g.smp_seed = m->dev.alloc<uint64_t>(B);
+    g.smp_scr = m->dev.alloc<float>(nscr);
+    ok = ok && g.smp_temp && g.smp_seed && g.smp_scr;
+  }
+  if (!ok) {
+    (void)hipGetLastError();  // the failed hipMalloc is handled here
+    for (DecGroup& g : m->groups) {
+      for (void* p : {(void*)g.smp_temp, (void*)g.smp_seed, (void*)g.smp_scr}) m->dev.release(p);
+      g.smp_temp = g.smp_scr = nullptr;
+      g.smp_seed = nullptr;
+    }
+    return fail(WQ4_ENOMEM, "sampling buffer allocation failed");
+  }
+  m->bytes += m->groups.size() * (B * 12 + nscr * 4);
+  m->sample_alloc_ok = true;
   return WQ4_OK;
 }
 

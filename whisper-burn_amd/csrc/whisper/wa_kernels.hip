@@ -15,6 +15,7 @@
 
 #include <cfloat>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../wq4_device.hpp"
 #include "../wq4_lnmath.hpp"
@@ -1367,6 +1368,253 @@ __device__ __forceinline__ void pick_from_lds_ts(const float* lg, int B, int V, 
   }
 }
 
+// ------------------------------------------------ temperature sampling --
+// Gumbel-max: argmax_v (z_v + T g_v), g i.i.d. standard Gumbel, is a draw
+// from softmax(z / T) -- the pick stays an argmax, over perturbed keys.  The
+// noise is a pure function of (clip seed, pick index, token id): splitmix64's
+// finaliser over a per-pick key, 23 bits to a uniform strictly inside (0, 1)
+// (exact in f32), g = -log(-log u) in [-2.82, 16.64].  The one definition,
+// shared by the fused kernel, the row kernel and the host (sample_noise).
+__host__ __device__ inline uint64_t smp_mix(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+__host__ __device__ inline uint64_t smp_pick_key(uint64_t seed, int pick) {
+  return smp_mix(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(pick + 1));
+}
+__host__ __device__ inline float smp_uniform(uint64_t k, int v) {
+  const uint32_t h = (uint32_t)(smp_mix(k ^ (uint64_t)v) >> 41);  // 23 bits
+  return ((float)h + 0.5f) * 0x1p-23f;                            // exact: 2 h + 1 < 2^24
+}
+__host__ __device__ inline float smp_gumbel(uint64_t k, int v) { return -logf(-logf(smp_uniform(k, v))); }
+// The key of logit z: a clip with T = 0 evaluates no noise; -inf stays -inf (g is finite).
+__device__ __forceinline__ float smp_key(float z, float T, uint64_t k, int v) {
+  return T > 0.0f ? fmaf(T, smp_gumbel(k, v), z) : z;
+}
+
+void sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out) {
+  const uint64_t k = smp_pick_key(seed, pick);
+  for (int i = 0; i < n; ++i) {
+    if (u_out) u_out[i] = smp_uniform(k, id0 + i);
+    if (g_out) g_out[i] = smp_gumbel(k, id0 + i);
+  }
+}
+
+// (key, index) as better_pair, carrying the raw logit at the index.
+__device__ __forceinline__ void better_key(float& bk, int& bi, float& bz, float k, int i, float z) {
+  if (k > bk || (k == bk && i > bi)) {
+    bk = k;
+    bi = i;
+    bz = z;
+  }
+}
+
+// What a sampled instantiation of the fused kernel takes beside TsArgs: the
+// clips' temperatures and seeds (read at run time, not baked into the graph)
+// and one scratch block scr [side][5][32][groups] f32 -- per side (0 text or
+// the whole row, 1 timestamps) the workgroups' key candidates (key, index,
+// raw logit there), raw maxima and exp sums relative to them.
+struct SampleArgs : TsArgs {
+  const float* temp;
+  const uint64_t* seed;
+  float* scr;
+};
+enum { kSmpKey = 0, kSmpIdx = 1, kSmpZ = 2, kSmpMax = 3, kSmpSum = 4, kSmpArrays = 5 };
+
+// pick_from_lds / pick_from_lds_ts of a sampled decode: each workgroup leaves
+// per row (and, TS, per side) its best key with the raw logit at it, its raw
+// maximum m_w and s_w = sum exp(z - m_w) -- the sums exactly as the unsampled
+// forms add them, so a T = 0 row repeats their bits -- and the last-arriving
+// workgroup merges M = max m_w, S = sum s_w exp(m_w - M), decides rule f from
+// the raw sums (TS; the noise never reaches it), picks the best key over the
+// surviving side(s) and writes lp = z_tok - M - log S, the untempered
+// log-probability.  The pick key k(seed, pick) is hashed once per thread.
+template <int TS>
+__device__ __forceinline__ void pick_from_lds_sample(const float* lg, int B, int V, int pick, const SampleArgs& a,
+                                                     int* __restrict__ counter, int* __restrict__ out_tok,
+                                                     float* __restrict__ out_lp, int* ticket) {
+  const int tid = threadIdx.x, nwg = gridDim.x;
+  const int ts0 = TS ? a.ts0 : V;              // plain rows: one side, every id on it
+  const int nT = min(nwg, (ts0 + 127) / 128);  // workgroups [0, nT) hold side-0 ids
+  const int jx0 = min(nwg, ts0 / 128);         // workgroups [jx0, nwg) hold side-1 ids
+  const bool has_t = (int)blockIdx.x < nT, has_x = TS && (int)blockIdx.x >= jx0;
+  __syncthreads();
+  const int row = tid >> 3, part = tid & 7;
+  const float T = row < B ? a.temp[row] : 0.0f;  // rows >= B: no noise
+  const uint64_t k = T > 0.0f ? smp_pick_key(a.seed[row], pick) : 0;
+  float tm = -INFINITY, xm = -INFINITY;                                    // raw maxima
+  float tk = -INFINITY, xk = -INFINITY, tz = -INFINITY, xz = -INFINITY;  // key candidates
+  int ti = -1, xi = -1;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int c = part * 16 + j;
+    const int idx = blockIdx.x * 128 + c;
+    const float z = lg[row * kLgPickLd + c];
+    if (idx < V) {
+      const float key = smp_key(z, T, k, idx);
+      if (!TS || idx < ts0) {
+        tm = fmaxf(tm, z);
+        better_key(tk, ti, tz, key, idx, z);
+      } else {
+        xm = fmaxf(xm, z);
+        better_key(xk, xi, xz, key, idx, z);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    tm = fmaxf(tm, __shfl_xor(tm, o, 64));
+    const float k2 = __shfl_xor(tk, o, 64), z2 = __shfl_xor(tz, o, 64);
+    const int i2 = __shfl_xor(ti, o, 64);
+    better_key(tk, ti, tz, k2, i2, z2);
+    if constexpr (TS) {
+      xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+      const float k3 = __shfl_xor(xk, o, 64), z3 = __shfl_xor(xz, o, 64);
+      const int i3 = __shfl_xor(xi, o, 64);
+      better_key(xk, xi, xz, k3, i3, z3);
+    }
+  }
+  // each side's sum relative to its own raw maximum; a side with every logit masked: 0
+  float s_t = 0.0f, s_x = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const int c = part * 16 + j;
+    const int idx = blockIdx.x * 128 + c;
+    const float v = lg[row * kLgPickLd + c];
+    if (idx < V) {
+      if (!TS || idx < ts0) {
+        if (tm > -INFINITY) s_t += expf(v - tm);
+      } else {
+        if (xm > -INFINITY) s_x += expf(v - xm);
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    s_t += __shfl_xor(s_t, o, 64);
+    if constexpr (TS) s_x += __shfl_xor(s_x, o, 64);
+  }
+  const uint32_t plane = 32u * nwg * 4u;  // bytes of one [32][groups] array
+  const __amdgpu_buffer_rsrc_t rs =
+      __builtin_amdgcn_make_buffer_rsrc(a.scr, 0, (TS ? 2 : 1) * kSmpArrays * plane, 0x00020000);
+  auto put = [&](int side, int arr, uint32_t off, uint32_t bits) {
+    __builtin_amdgcn_raw_buffer_store_b32(bits, rs, (uint32_t)(side * kSmpArrays + arr) * plane + off, 0, 16);  // sc1
+  };
+  auto get = [&](int side, int arr, uint32_t off) {
+    return __builtin_amdgcn_raw_buffer_load_b32(rs, (uint32_t)(side * kSmpArrays + arr) * plane + off, 0, 16);
+  };
+  auto f2u = [](float f) { return __builtin_bit_cast(uint32_t, f); };
+  auto u2f = [](uint32_t u) { return __builtin_bit_cast(float, u); };
+  if (part == 0 && row < B) {
+    const uint32_t off = (uint32_t)(row * nwg + blockIdx.x) * 4;  // < plane: row < 32, blockIdx.x < nwg
+    if (has_t) {
+      put(0, kSmpKey, off, f2u(tk));
+      put(0, kSmpIdx, off, (uint32_t)ti);
+      put(0, kSmpZ, off, f2u(tz));
+      put(0, kSmpMax, off, f2u(tm));
+      put(0, kSmpSum, off, f2u(s_t));
+    }
+    if (has_x) {
+      put(1, kSmpKey, off, f2u(xk));
+      put(1, kSmpIdx, off, (uint32_t)xi);
+      put(1, kSmpZ, off, f2u(xz));
+      put(1, kSmpMax, off, f2u(xm));
+      put(1, kSmpSum, off, f2u(s_x));
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    typedef __attribute__((address_space(1))) int gint;
+    const int prev = __hip_atomic_fetch_add((gint*)counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *ticket = prev == nwg - 1;
+  }
+  __syncthreads();
+  if (!*ticket) return;
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler-only: loads stay below the ticket
+  tm = xm = tk = xk = tz = xz = -INFINITY;
+  ti = xi = -1;
+  if (row < B) {
+    for (int j = part; j < nT; j += 8) {
+      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+      tm = fmaxf(tm, u2f(get(0, kSmpMax, off)));
+      better_key(tk, ti, tz, u2f(get(0, kSmpKey, off)), (int)get(0, kSmpIdx, off), u2f(get(0, kSmpZ, off)));
+    }
+    if constexpr (TS)
+      for (int j = jx0 + part; j < nwg; j += 8) {
+        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+        xm = fmaxf(xm, u2f(get(1, kSmpMax, off)));
+        better_key(xk, xi, xz, u2f(get(1, kSmpKey, off)), (int)get(1, kSmpIdx, off), u2f(get(1, kSmpZ, off)));
+      }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    tm = fmaxf(tm, __shfl_xor(tm, o, 64));
+    const float k2 = __shfl_xor(tk, o, 64), z2 = __shfl_xor(tz, o, 64);
+    const int i2 = __shfl_xor(ti, o, 64);
+    better_key(tk, ti, tz, k2, i2, z2);
+    if constexpr (TS) {
+      xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+      const float k3 = __shfl_xor(xk, o, 64), z3 = __shfl_xor(xz, o, 64);
+      const int i3 = __shfl_xor(xi, o, 64);
+      better_key(xk, xi, xz, k3, i3, z3);
+    }
+  }
+  // tm = M (M_text), xm = M_ts in the row's 8 threads: the sums again, rescaled to them
+  float S_t = 0.0f, S_x = 0.0f;
+  if (row < B) {
+    if (tm > -INFINITY)
+      for (int j = part; j < nT; j += 8) {
+        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+        S_t += u2f(get(0, kSmpSum, off)) * expf(u2f(get(0, kSmpMax, off)) - tm);
+      }
+    if constexpr (TS)
+      if (xm > -INFINITY)
+        for (int j = jx0 + part; j < nwg; j += 8) {
+          const uint32_t off = (uint32_t)(row * nwg + j) * 4;
+          S_x += u2f(get(1, kSmpSum, off)) * expf(u2f(get(1, kSmpMax, off)) - xm);
+        }
+  }
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) {
+    S_t += __shfl_xor(S_t, o, 64);
+    if constexpr (TS) S_x += __shfl_xor(S_x, o, 64);
+  }
+  if (part == 0 && row < B) {
+    // lpg = -log sum exp(z - Ms) over the surviving side(s), Ms their raw
+    // maximum, as the unsampled forms write it; the sampled token is d = z_tok
+    // - Ms below that (d = 0: the greedy token, their bits)
+    int tok = ti, mass = 0;
+    float lpg, Ms = tm, zt = tz;
+    if constexpr (TS) {
+      int unused;
+      ts_decide(tm, 0, S_t, xm, 0, S_x, unused, lpg, mass);
+      if (mass) {
+        Ms = xm;
+        tok = xi;
+        zt = xz;
+      } else {
+        Ms = fmaxf(tm, xm);
+        better_key(tk, tok, zt, xk, xi, xz);
+      }
+      if (a.out_mass) a.out_mass[row] = mass;
+    } else {
+      lpg = -logf(S_t);
+    }
+    const float d = zt - Ms;
+    out_tok[row] = tok < 0 ? 0 : tok;
+    out_lp[row] = d == 0.0f ? lpg : d + lpg;
+  }
+  if (tid == 0) {
+    typedef __attribute__((address_space(1))) int gint;
+    __hip_atomic_store((gint*)counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
+  }
+}
+
 constexpr int kLg2Chunk = 128;
 // 16-row groups of the fragment-tiled table (V padded to 128-row workgroups)
 __host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 127) / 128 * 8; }
@@ -1388,12 +1636,17 @@ __host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 12
 // TS = 1 (timestamp transcribes): the masks of the rows' rule records
 // (ts_masked) while lg[] is written, and pick_from_lds_ts; `ts` is read by
 // that instantiation only.
-template <int NS, int SCORE = 0, int TS = 0>
+// SAMPLE = 1 (sampled transcribes, with SCORE; with or without TS): the pick
+// is pick_from_lds_sample over Gumbel-perturbed keys at pick index
+// state->step + 1; its arguments ride behind TsArgs (SampleArgs), so the
+// other instantiations keep their argument lists.
+template <int NS, int SCORE = 0, int TS = 0, int SAMPLE = 0>
 __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
     const _Float16* __restrict__ htiled, int B, int D, const _Float16* __restrict__ emb2, int V, int min_tokens,
     const DecodeState* __restrict__ state, float* __restrict__ pval, int* __restrict__ pidx, int* __restrict__ counter,
     int* __restrict__ out_tok, const int* __restrict__ trace_ids, float* __restrict__ trace_out, int trace_s1,
-    int trace_k, int* __restrict__ range_flag, float* __restrict__ psum, float* __restrict__ out_lp, TsArgs ts) {
+    int trace_k, int* __restrict__ range_flag, float* __restrict__ psum, float* __restrict__ out_lp,
+    std::conditional_t<SAMPLE != 0, SampleArgs, TsArgs> ts) {
   constexpr int KS = kLg2Chunk / 32;             // Q4-block-sized k-steps per chunk
   constexpr int HCH = KS * 2 * NS * 1024;        // bytes of hidden fragments per chunk
   static_assert(HCH % (256 * 16) == 0, "whole glds rounds");
@@ -1527,7 +1780,9 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
         if (id >= 0 && id < 128) trace_out[o] = lg[b * kLgPickLd + id];
       }
   }
-  if constexpr (TS)
+  if constexpr (SAMPLE)
+    pick_from_lds_sample<TS>(lg, B, V, state->step + 1, ts, counter, out_tok, out_lp, ticket);
+  else if constexpr (TS)
     pick_from_lds_ts(lg, B, V, ts, pval, pidx, psum, counter, out_tok, out_lp, ticket);
   else
     pick_from_lds<SCORE>(lg, B, V, pval, pidx, psum, counter, out_tok, out_lp, ticket);
@@ -1916,6 +2171,172 @@ hipError_t launch_bookkeep_ts(const int* next_tok, const float* next_lp, int* to
                               int ts0, int V, hipStream_t st) {
   hipLaunchKernelGGL(bookkeep_ts_kernel, dim3(1), dim3(256), 0, st, next_tok, next_lp, tokens, logprob, n_tokens, done,
                      B, max_tokens, eot_stop, state, rules, ts0, V);
+  return hipGetLastError();
+}
+
+// ------------------------------------ temperature sampling, launches --
+// Behind the timestamp kernels, for the same reason they are behind the rest.
+int64_t logits_sample_scratch_floats(int V) { return (int64_t)2 * kSmpArrays * 32 * logits_argmax_groups(V); }
+
+hipError_t launch_logits_argmax_sample(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
+                                       int min_tokens, const DecodeState* state, const float* temp,
+                                       const uint64_t* seed, const TsRule* rules, int ts0, float* scr, int* counter,
+                                       int* out_tok, float* out_lp, int* out_mass, const int* trace_ids,
+                                       float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st) {
+  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled || !out_lp || !temp || !seed || !scr ||
+      (rules && ts0 < 1))
+    return hipErrorInvalidValue;
+  const dim3 grid(logits_argmax_groups(V));
+  SampleArgs a{};
+  a.rules = rules;
+  a.ts0 = ts0;
+  a.out_mass = out_mass;
+  a.temp = temp;
+  a.seed = seed;
+  a.scr = scr;
+  float* const nf = nullptr;
+  int* const ni = nullptr;
+#define WA_SAMPLE_LAUNCH(NS_, TS_)                                                                                  \
+  hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<NS_, 1, TS_, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V, \
+                     min_tokens, state, nf, ni, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,           \
+                     range_flag, nf, out_lp, a)
+  if (rules) {
+    if (ns == 2)
+      WA_SAMPLE_LAUNCH(2, 1);
+    else
+      WA_SAMPLE_LAUNCH(1, 1);
+  } else {
+    if (ns == 2)
+      WA_SAMPLE_LAUNCH(2, 0);
+    else
+      WA_SAMPLE_LAUNCH(1, 0);
+  }
+#undef WA_SAMPLE_LAUNCH
+  return hipGetLastError();
+}
+
+// ---------------------------------------------- sampled pick of a row --
+// The sampled pick over a stored logit row (the prompt's pick, pick 0, and
+// decode groups wider than 32 rows), plain (rules null: EOT suppression only,
+// the whole row one side) or under the timestamp rule: row_logprob_kernel's /
+// row_timestamp_kernel's two passes and order of additions, with each side's
+// best key carried beside its raw maximum; thread 0 decides as
+// pick_from_lds_sample does.
+__global__ __launch_bounds__(256) void row_sample_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                         int suppress_fixed, int min_tokens,
+                                                         const DecodeState* __restrict__ state,
+                                                         const TsRule* __restrict__ rules, int ts0_rule,
+                                                         const float* __restrict__ temp,
+                                                         const uint64_t* __restrict__ seed, int pick_fixed,
+                                                         int* __restrict__ out_tok, float* __restrict__ out_lp,
+                                                         int* __restrict__ out_mass, int* __restrict__ range_flag) {
+  __shared__ float sm[2][4], sk[2][4], sz[2][4], ss[2][4];
+  __shared__ int si[2][4];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float* z = logits + (size_t)b * ld;
+  const bool suppress = state ? (state->step + 1 < min_tokens) : suppress_fixed != 0;
+  const int pick = state ? state->step + 1 : pick_fixed;
+  const int ts0 = rules ? ts0_rule : V;
+  int4 rule = {};
+  if (rules) rule = *reinterpret_cast<const int4*>(rules + b);
+  auto masked = [&](int i) { return rules ? ts_masked(i, ts0, rule, suppress) : (suppress && i == kEOT); };
+  const float T = temp[b];
+  const uint64_t k = T > 0.0f ? smp_pick_key(seed[b], pick) : 0;
+  float tm = -INFINITY, xm = -INFINITY, tk = -INFINITY, xk = -INFINITY, tz = -INFINITY, xz = -INFINITY;
+  int ti = -1, xi = -1;
+  bool bad = false;
+  for (int i = tid; i < V; i += 256) {
+    float v = z[i];
+    bad |= !__builtin_isfinite(v);
+    if (masked(i)) v = -INFINITY;
+    const float key = smp_key(v, T, k, i);
+    if (i < ts0) {
+      tm = fmaxf(tm, v);
+      better_key(tk, ti, tz, key, i, v);
+    } else {
+      xm = fmaxf(xm, v);
+      better_key(xk, xi, xz, key, i, v);
+    }
+  }
+  if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    tm = fmaxf(tm, __shfl_xor(tm, o, 64));
+    xm = fmaxf(xm, __shfl_xor(xm, o, 64));
+    const float k2 = __shfl_xor(tk, o, 64), z2 = __shfl_xor(tz, o, 64);
+    const float k3 = __shfl_xor(xk, o, 64), z3 = __shfl_xor(xz, o, 64);
+    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
+    better_key(tk, ti, tz, k2, i2, z2);
+    better_key(xk, xi, xz, k3, i3, z3);
+  }
+  if (lane == 0) {
+    sm[0][wave] = tm;
+    sk[0][wave] = tk;
+    sz[0][wave] = tz;
+    si[0][wave] = ti;
+    sm[1][wave] = xm;
+    sk[1][wave] = xk;
+    sz[1][wave] = xz;
+    si[1][wave] = xi;
+  }
+  __syncthreads();
+  tm = xm = tk = xk = tz = xz = -INFINITY;
+  ti = xi = -1;
+  for (int w = 0; w < 4; ++w) {
+    tm = fmaxf(tm, sm[0][w]);
+    xm = fmaxf(xm, sm[1][w]);
+    better_key(tk, ti, tz, sk[0][w], si[0][w], sz[0][w]);
+    better_key(xk, xi, xz, sk[1][w], si[1][w], sz[1][w]);
+  }
+  float s_t = 0.0f, s_x = 0.0f;
+  for (int i = tid; i < V; i += 256) {
+    const float v = masked(i) ? -INFINITY : z[i];
+    if (i < ts0) {
+      if (tm > -INFINITY) s_t += expf(v - tm);
+    } else {
+      if (xm > -INFINITY) s_x += expf(v - xm);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s_t += __shfl_xor(s_t, o, 64);
+    s_x += __shfl_xor(s_x, o, 64);
+  }
+  if (lane == 0) {
+    ss[0][wave] = s_t;
+    ss[1][wave] = s_x;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    s_t = ((ss[0][0] + ss[0][1]) + ss[0][2]) + ss[0][3];
+    s_x = ((ss[1][0] + ss[1][1]) + ss[1][2]) + ss[1][3];
+    int unused, mass;
+    float lpg;
+    ts_decide(tm, 0, s_t, xm, 0, s_x, unused, lpg, mass);  // an empty timestamp side: -log s_t, no mass
+    int tok = ti;
+    float Ms = fmaxf(tm, xm), zt = tz;
+    if (mass) {
+      Ms = xm;
+      tok = xi;
+      zt = xz;
+    } else {
+      better_key(tk, tok, zt, xk, xi, xz);
+    }
+    const float d = zt - Ms;
+    out_tok[b] = tok < 0 ? 0 : tok;
+    if (out_lp) out_lp[b] = d == 0.0f ? lpg : d + lpg;
+    if (out_mass) out_mass[b] = mass;
+  }
+}
+
+hipError_t launch_row_sample(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
+                             const DecodeState* state, const TsRule* rules, int ts0, const float* temp,
+                             const uint64_t* seed, int pick, int* out_tok, float* out_lp, int* out_mass,
+                             int* range_flag, hipStream_t st) {
+  if (rows < 1 || V < 1 || V > ld || !logits || !out_tok || !temp || !seed || (rules && ts0 < 1) || pick < 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(row_sample_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, suppress_eot, min_tokens, state,
+                     rules, ts0, temp, seed, pick, out_tok, out_lp, out_mass, range_flag);
   return hipGetLastError();
 }
 

@@ -246,4 +246,37 @@ hipError_t launch_bookkeep_ts(const int* next_tok, const float* next_lp, int* to
                               int* done, int B, int max_tokens, int eot_stop, DecodeState* state, TsRule* rules,
                               int ts0, int V, hipStream_t st);
 
+// ---- temperature sampling (wa_transcribe_sampled) -------------------------
+// Gumbel-max over counter-based noise, all integer arithmetic uint64 and
+// wrapping, mix = splitmix64's finaliser:
+//   k(seed, pick)    = mix(seed + 0x9E3779B97F4A7C15 * (pick + 1))
+//   h(seed, pick, v) = mix(k ^ v) >> 41                  (23 bits)
+//   u = (h + 0.5) * 2^-23   g = -log(-log(u))   key_v = fmaf(T, g, z_v)
+// pick = 0 for the prompt's pick, DecodeState::step + 1 for a decode step's.
+// A row with T = 0 evaluates no noise: its key is z and its pick the greedy
+// one.  The pick is the largest key, the largest index among equal keys; its
+// score is the untempered log softmax(z)[tok] over the masked row.
+// sample_noise: u and g of ids id0 .. id0 + n - 1 on the host (either nullable).
+void sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out);
+// Floats of the sampled fused launch's scratch block `scr`.
+int64_t logits_sample_scratch_floats(int V);
+// The sampled form of launch_logits_argmax_scored (rules null) or of
+// launch_logits_argmax_ts (rules non-null: masks a-e as there, rule f from the
+// raw sums, the pick over the surviving side or sides): temp / seed device
+// [B], read when the kernel runs; scr: logits_sample_scratch_floats(V) floats
+// (per side and workgroup the key candidate with its raw logit, the raw
+// maximum and the exp sum relative to it).
+hipError_t launch_logits_argmax_sample(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
+                                       int min_tokens, const DecodeState* state, const float* temp,
+                                       const uint64_t* seed, const TsRule* rules, int ts0, float* scr, int* counter,
+                                       int* out_tok, float* out_lp, int* out_mass, const int* trace_ids,
+                                       float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st);
+// The same over stored logit rows [rows][ld] (the prompt's pick, decode groups
+// wider than 32 rows): pick index `pick`, or state->step + 1 when state is
+// non-null; EOT suppression as launch_row_timestamp.
+hipError_t launch_row_sample(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
+                             const DecodeState* state, const TsRule* rules, int ts0, const float* temp,
+                             const uint64_t* seed, int pick, int* out_tok, float* out_lp, int* out_mass,
+                             int* range_flag, hipStream_t st);
+
 }  // namespace wa

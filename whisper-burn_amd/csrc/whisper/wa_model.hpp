@@ -159,12 +159,20 @@ struct DecGroup {
   TsRule* ts_rules = nullptr;
   float *lg_xval = nullptr, *lg_xsum = nullptr;
   int* lg_xidx = nullptr;
+  // sampled transcribes (wa_transcribe_sampled; allocated by the first one,
+  // ensure_sample_buffers): the clips' temperatures and seeds, uploaded by
+  // every prompt from the caller's arrays at clip `clip0` of them, and the
+  // sampled fused kernel's scratch block (launch_logits_argmax_sample)
+  float* smp_temp = nullptr;
+  uint64_t* smp_seed = nullptr;
+  float* smp_scr = nullptr;
+  int clip0 = 0;  // this group's first clip in the call's per-clip host arrays (run_decode)
   DecodeState* state;
   void* ffn_ws = nullptr;  // range tier 2: wq4_ffn_forward_ws workspace (4 * nb rows)
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (timestamps, scoring, lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
+  int64_t graph_key = -1;  // (sampling, timestamps, scoring, lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
   // graphs of other layouts this group ran (ensure_graph): a call of units of
   // three and two, with and without the masked stream beside them, goes
   // through four keys per group and comes back to each
@@ -274,6 +282,19 @@ struct wa_model {
   int ts_max_initial = 50;
   bool ts_alloc_ok = false;  // every group's timestamp buffers allocated (ensure_ts_buffers)
   int ts0() const { return cfg.no_timestamps_token() + 1; }  // <|0.00|>
+  // a sampled transcribe is running (wa_transcribe_sampled /
+  // wa_transcribe_batches_sampled / wa_transcribe_fallback; `score` is set
+  // with it, `ts` when it decodes timestamps): every pick is the Gumbel-max
+  // pick at the clip's temperature and seed -- host arrays over the call's
+  // clips, read by the prompts.  frozen (nullable, host, per clip of the
+  // batch): clips that start the decode done -- their picks go nowhere and
+  // the decode stops once the live clips emitted EOT (the fallback ladder's
+  // re-decodes).
+  bool sample = false;
+  const float* smp_temp = nullptr;
+  const uint64_t* smp_seed = nullptr;
+  const uint8_t* frozen = nullptr;
+  bool sample_alloc_ok = false;  // every group's sampling buffers allocated (ensure_sample_buffers)
   // live kernel timing (wa_profile_*)
   struct Pending {
     hipEvent_t a, b;
@@ -343,6 +364,7 @@ wq4_status alloc_activations(wa_model* m);
 wq4_status ensure_ffn_ws(wa_model* m);
 wq4_status ensure_score_buffers(wa_model* m);
 wq4_status ensure_ts_buffers(wa_model* m);
+wq4_status ensure_sample_buffers(wa_model* m);
 int decode_groups(int B);
 wq4_status encoder_front(wa_model* m, const float* mel, int B, hipStream_t st);
 wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);

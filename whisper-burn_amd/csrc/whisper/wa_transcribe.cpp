@@ -1,6 +1,8 @@
 // wa_transcribe.cpp -- the transcribe drivers (WhisperModel::transcribe,
 // src/model/whisper.rs:51-128): one batch, software-pipelined batches, and
 // the range-tier retries around them.
+#include <cmath>
+
 #include "wa_model.hpp"
 
 using namespace wa;
@@ -115,8 +117,11 @@ int unit_groups(int B, int n) { return n > 1 ? n : decode_groups(B); }
 // the CUs it leaves them (kXattnPeerCUs), so HBM idles less than beside one
 // chain (measurements and the sweeps of kXattnPeerCUs and the residency
 // budget at three lanes: DESIGN.md section 10).
+// batch0: the index, among the call's batches, of the batch in lane 0 -- where
+// the groups' clips sit in the call's per-clip host arrays (DecGroup::clip0).
 wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token, int max_tokens, int eot_stop,
-                      hipEvent_t ready, const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps) {
+                      hipEvent_t ready, const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps,
+                      int batch0 = 0) {
   const int G = unit_groups(B, n);
   // the groups decode concurrently: the planes of all their clips are live
   // (every lane of a unit), which decides the share each keeps cached
@@ -135,6 +140,7 @@ wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token,
     g.lane = n > 1 ? i : 0;
     g.b0 = n > 1 ? 0 : (int)((int64_t)B * i / G);
     g.nb = n > 1 ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
+    g.clip0 = (batch0 + g.lane) * B + g.b0;
     WA_HIP(hipStreamWaitEvent(g.st, ready, 0));
     WA_TRY(prompt_group(m, g, lang_token, g.st));
     WA_HIP(hipEventRecord(gprompt[i], g.st));
@@ -245,9 +251,12 @@ void copy_scores(const float* sc, int B, int max_tokens, const wa_scores* out, s
 // One transcribe (whisper.rs:51-128 for a batch of clips); *overflow = the
 // range flag of this run (see wa_model::range_flag).  scores (a scored
 // transcribe, m->score; null otherwise): this run's scores too.
+// reuse_enc (the fallback ladder's re-decodes): no encoder pass -- the prompt
+// and the loop run again over the planes (and few-clip caches) the last pass
+// left, and the prompt / decode times and steps are added to the timings.
 wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                            int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, bool* overflow,
-                           const wa_scores* scores) {
+                           const wa_scores* scores, bool reuse_enc = false) {
   // all work on the model's own stream, ordered after the caller's stream
   hipStream_t st = m->own_stream;
   const int B = n_clips;
@@ -264,9 +273,9 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
   WA_HIP(hipMemsetAsync(m->range_flag, 0, sizeof(int), st));
 
   WA_HIP(hipEventRecord(e_enc, st));
-  WA_TRY(encoder_forward(m, mel_dev, B, st, nullptr));
+  if (!reuse_enc) WA_TRY(encoder_forward(m, mel_dev, B, st, nullptr));
   WA_HIP(hipEventRecord(e_kv, st));
-  WA_TRY(cross_kv_forward(m, B, st, true));
+  if (!reuse_enc) WA_TRY(cross_kv_forward(m, B, st, true));
   WA_HIP(hipEventRecord(e_ready, st));
   // decode groups: contiguous clip ranges on their own streams, started
   // after the encoder-planes pass, joined back into `st` at the end
@@ -292,6 +301,12 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
     tp = std::max(tp, t);
   }
   WA_HIP(hipEventElapsedTime(&tall, e_ready, e_end));
+  if (reuse_enc) {
+    m->timings[2] += tp;
+    m->timings[3] += tall - tp;
+    m->timings[4] += (float)steps;
+    return WQ4_OK;
+  }
   m->timings[0] = t_enc;
   m->timings[1] = t_kv;
   m->timings[2] = tp;
@@ -484,7 +499,7 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
     }
     // the masked part above takes its CUs from this decode; the last unit has them all
     WA_TRY(run_decode(m, B, u.n, i + 1 < NU ? m->enc_cus : 0, lang_token, max_tokens, eot_stop, u.ready, u.gprompt,
-                      u.gdone, u.gsteps));
+                      u.gdone, u.gsteps, u.first));
     int32_t* hb = host + (size_t)u.first * per;
     WA_TRY(collect_batch(m, B, u.n, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
                          per, scores ? reinterpret_cast<float*>(hb + per0) : nullptr));
@@ -568,6 +583,46 @@ static wq4_status with_timestamps(wa_model* m, int max_initial, Run run) {
   return s;
 }
 
+// The sampling mode around a transcribe: the score, sampling and (timestamps)
+// rule buffers, then m->sample with m->score (and m->ts) and the call's
+// per-clip temperatures and seeds for the length of `run`.
+template <class Run>
+static wq4_status with_sampling(wa_model* m, const float* temp, const uint64_t* seed, int timestamps, int max_initial,
+                                Run run) {
+  WA_HIP(hipSetDevice(m->device));
+  WA_TRY(ensure_score_buffers(m));
+  if (timestamps) WA_TRY(ensure_ts_buffers(m));
+  WA_TRY(ensure_sample_buffers(m));
+  m->score = m->sample = true;
+  m->ts = timestamps != 0;
+  if (timestamps) m->ts_max_initial = max_initial;
+  m->smp_temp = temp;
+  m->smp_seed = seed;
+  const wq4_status s = run();
+  m->score = m->sample = m->ts = false;
+  m->smp_temp = nullptr;
+  m->smp_seed = nullptr;
+  m->frozen = nullptr;
+  return s;
+}
+
+static bool bad_temperatures(const float* t, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!(t[i] >= 0.0f) || !std::isfinite(t[i])) return true;
+  return false;
+}
+
+// One range tier up after a flagged run (see transcribe_tiers); WQ4_ERANGE at the last.
+static wq4_status raise_tier(wa_model* m) {
+  if (m->range_tier == 3)
+    return fail(WQ4_ERANGE,
+                "activation overflow: an MFMA operand left the f16-pair range (|x| >= 4094 after every range tier: "
+                "LayerNorm path, per-call FFN and attention-projection operand scales) and the logits are not finite");
+  if (m->range_tier == 1) WA_TRY(ensure_ffn_ws(m));  // entering tier 2
+  ++m->range_tier;
+  return WQ4_OK;
+}
+
 extern "C" {
 
 // wa_transcribe, and wa_transcribe_scored with its scores: the scores are
@@ -586,12 +641,7 @@ static wq4_status transcribe_tiers(wa_model* m, const float* mel_dev, int n_clip
     WA_TRY(transcribe_once(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
                            &overflow, scores));
     if (!overflow) return WQ4_OK;
-    if (m->range_tier == 3)
-      return fail(WQ4_ERANGE,
-                  "activation overflow: an MFMA operand left the f16-pair range (|x| >= 4094 after every range tier: "
-                  "LayerNorm path, per-call FFN and attention-projection operand scales) and the logits are not finite");
-    if (m->range_tier == 1) WA_TRY(ensure_ffn_ws(m));  // entering tier 2
-    ++m->range_tier;
+    WA_TRY(raise_tier(m));
   }
 }
 
@@ -643,9 +693,20 @@ static wq4_status transcribe_batches(wa_model* m, const float* mel_dev, int n_ba
       at.lang_token = scores->lang_token ? scores->lang_token + c0 : nullptr;
       at.lang_prob = scores->lang_prob ? scores->lang_prob + c0 : nullptr;
     }
-    WA_TRY(transcribe_tiers(m, mel_dev + i * mel_stride, n_clips, lang_token, max_tokens, eot_stop,
-                            tokens_out + (size_t)i * n_clips * max_tokens, n_tokens_out + (size_t)i * n_clips, stream,
-                            scores ? &at : nullptr));
+    // a sampled call: batch i's temperatures and seeds lead the per-clip arrays for the re-run
+    const float* const temp = m->smp_temp;
+    const uint64_t* const seed = m->smp_seed;
+    if (m->sample) {
+      m->smp_temp = temp + (size_t)i * n_clips;
+      m->smp_seed = seed + (size_t)i * n_clips;
+    }
+    const wq4_status rs =
+        transcribe_tiers(m, mel_dev + i * mel_stride, n_clips, lang_token, max_tokens, eot_stop,
+                         tokens_out + (size_t)i * n_clips * max_tokens, n_tokens_out + (size_t)i * n_clips, stream,
+                         scores ? &at : nullptr);
+    m->smp_temp = temp;
+    m->smp_seed = seed;
+    WA_TRY(rs);
   }
   return WQ4_OK;
 }
@@ -702,6 +763,116 @@ wq4_status wa_transcribe_batches_timestamps(wa_model* m, const float* mel_dev, i
     return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
                               n_tokens_out, stream, scores);
   });
+}
+
+wq4_status wa_transcribe_sampled(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                 int eot_stop, const wa_sampling* sampling, int32_t* tokens_out,
+                                 int32_t* n_tokens_out, const wa_scores* scores, void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !sampling || !sampling->temperature || !sampling->seed)
+    return fail(WQ4_EINVAL, "null argument");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (n_clips >= 1 && bad_temperatures(sampling->temperature, n_clips))
+    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  return with_sampling(m, sampling->temperature, sampling->seed, sampling->timestamps, sampling->max_initial, [&] {
+    return transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
+                            scores);
+  });
+}
+
+wq4_status wa_transcribe_batches_sampled(wa_model* m, const float* mel_dev, int n_batches, int n_clips,
+                                         int lang_token, int max_tokens, int eot_stop, const wa_sampling* sampling,
+                                         int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
+                                         void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !sampling || !sampling->temperature || !sampling->seed)
+    return fail(WQ4_EINVAL, "null argument");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
+  if (n_clips >= 1 && bad_temperatures(sampling->temperature, n_batches * n_clips))
+    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  return with_sampling(m, sampling->temperature, sampling->seed, sampling->timestamps, sampling->max_initial, [&] {
+    return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
+                              n_tokens_out, stream, scores);
+  });
+}
+
+// The temperature fallback ladder: one encoder pass, then per rung a prompt +
+// decode over the same planes with the clips that have passed frozen.
+wq4_status wa_transcribe_fallback(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                  int eot_stop, const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
+                                  const wa_scores* scores, int32_t* rung_out, void* stream) {
+  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !fb || !fb->temperatures || !fb->seed)
+    return fail(WQ4_EINVAL, "null argument");
+  if (fb->n_temperatures < 1 || fb->n_temperatures > 8) return fail(WQ4_EINVAL, "the ladder has 1 .. 8 rungs");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (bad_temperatures(fb->temperatures, fb->n_temperatures))
+    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
+  const int B = n_clips, R = fb->n_temperatures;
+  const size_t slots = (size_t)max_tokens + 1;
+  std::vector<float> temp(B);
+  std::vector<uint64_t> seed(B);
+  return with_sampling(m, temp.data(), seed.data(), fb->timestamps, fb->max_initial, [&]() -> wq4_status {
+    // one rung's results; the clips it was run for are copied to the caller's arrays
+    std::vector<int32_t> tok((size_t)B * max_tokens), nt(B), lt(B);
+    std::vector<float> lp((size_t)B * slots), ns(B), lpr(B);
+    const wa_scores rung_scores{lp.data(), ns.data(), lt.data(), lpr.data()};
+    for (;;) {  // the range tiers: a flagged rung restarts the ladder one tier up
+      bool overflow = false;
+      std::vector<uint8_t> frozen(B, 0);
+      int n_frozen = 0;
+      for (int r = 0; r < R && n_frozen < B && !overflow; ++r) {
+        for (int c = 0; c < B; ++c) {
+          temp[c] = fb->temperatures[r];
+          seed[c] = fb->seed[c] + (uint64_t)r;
+        }
+        m->frozen = r > 0 ? frozen.data() : nullptr;
+        WA_TRY(transcribe_once(m, mel_dev, B, lang_token, max_tokens, eot_stop, tok.data(), nt.data(), stream,
+                               &overflow, &rung_scores, r > 0));
+        if (overflow) break;
+        for (int c = 0; c < B; ++c) {
+          if (frozen[c]) continue;
+          std::memcpy(tokens_out + (size_t)c * max_tokens, tok.data() + (size_t)c * max_tokens, (size_t)max_tokens * 4);
+          n_tokens_out[c] = nt[c];
+          if (rung_out) rung_out[c] = r;
+          if (scores) {
+            if (scores->token_logprob)
+              std::memcpy(scores->token_logprob + c * slots, lp.data() + c * slots, slots * 4);
+            if (scores->no_speech_prob) scores->no_speech_prob[c] = ns[c];
+            if (scores->lang_token) scores->lang_token[c] = lt[c];
+            if (scores->lang_prob) scores->lang_prob[c] = lpr[c];
+          }
+          // the ladder rule: the mean of the stored log-probabilities below the
+          // threshold, unless the no-speech score calls the clip silence
+          // (comparisons with a NaN threshold are false: that test is off)
+          double sum = 0.0;
+          int cnt = 0;
+          for (size_t i = 0; i < slots; ++i) {
+            const float v = lp[c * slots + i];
+            if (!std::isnan(v)) {
+              sum += v;
+              ++cnt;
+            }
+          }
+          const double mean = cnt ? sum / cnt : 0.0;
+          const bool needs = mean < (double)fb->logprob_threshold && !(ns[c] > fb->no_speech_threshold);
+          if (!needs) {
+            frozen[c] = 1;
+            ++n_frozen;
+          }
+        }
+      }
+      if (!overflow) return WQ4_OK;
+      WA_TRY(raise_tier(m));
+    }
+  });
+}
+
+wq4_status wa_sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out) {
+  if (pick < 0 || id0 < 0 || n < 0 || (n > 0 && !u_out && !g_out)) return fail(WQ4_EINVAL, "bad arguments");
+  sample_noise(seed, pick, id0, n, u_out, g_out);
+  return WQ4_OK;
 }
 
 // OpenAI transcribe.py's slicing of one window's tokens at consecutive

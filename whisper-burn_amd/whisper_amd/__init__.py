@@ -36,6 +36,22 @@ class Segment(ctypes.Structure):
                 ("tok_end", ctypes.c_int32)]
 
 
+class Sampling(ctypes.Structure):
+    """struct wa_sampling: per-clip host temperatures and seeds of a sampled transcribe."""
+
+    _fields_ = [("temperature", ctypes.POINTER(ctypes.c_float)), ("seed", ctypes.POINTER(ctypes.c_uint64)),
+                ("timestamps", ctypes.c_int), ("max_initial", ctypes.c_int)]
+
+
+class Fallback(ctypes.Structure):
+    """struct wa_fallback: the temperature ladder, its thresholds and the clips' seeds."""
+
+    _fields_ = [("temperatures", ctypes.POINTER(ctypes.c_float)), ("n_temperatures", ctypes.c_int),
+                ("logprob_threshold", ctypes.c_float), ("no_speech_threshold", ctypes.c_float),
+                ("seed", ctypes.POINTER(ctypes.c_uint64)), ("timestamps", ctypes.c_int),
+                ("max_initial", ctypes.c_int)]
+
+
 RULE_FIELDS = ("text_ok", "ts_lo", "ts_hi", "first", "last", "penult", "t_last", "pad")  # a rule record's 8 int32
 
 
@@ -131,6 +147,20 @@ def lib() -> ctypes.CDLL:
         for n in ("wa_transcribe_timestamps", "wa_transcribe_batches_timestamps", "wa_segments_from_tokens",
                   "wa_timestamp_rule", "wa_logits_timestamp_check", "wa_row_timestamp_check",
                   "wa_timestamp_bookkeep_check"):
+            getattr(L, n).restype = c_int
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.wa_transcribe_sampled.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Sampling), i32p, i32p,
+                                            sp, vp]
+        L.wa_transcribe_batches_sampled.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int,
+                                                    ctypes.POINTER(Sampling), i32p, i32p, sp, vp]
+        L.wa_transcribe_fallback.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Fallback), i32p, i32p,
+                                             sp, i32p, vp]
+        L.wa_sample_noise.argtypes = [ctypes.c_uint64, c_int, c_int, c_int, f32p, f32p]
+        L.wa_logits_sample_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, f32p, u64p, c_int, i32p,
+                                             vp, vp, vp, vp]
+        L.wa_row_sample_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, f32p, u64p, c_int, i32p, vp, vp, vp]
+        for n in ("wa_transcribe_sampled", "wa_transcribe_batches_sampled", "wa_transcribe_fallback",
+                  "wa_sample_noise", "wa_logits_sample_check", "wa_row_sample_check"):
             getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
@@ -434,6 +464,70 @@ def timestamp_bookkeep_check(tokens, ts0: int, V: int, max_initial: int = 50, de
     return out
 
 
+def sample_noise(seed: int, pick: int, id0: int, n: int) -> tuple[np.ndarray, np.ndarray]:
+    """The sampling noise of ids id0 .. id0 + n - 1 at (seed, pick) as the
+    kernels define it (wa_sample_noise; host only): (u, g) float32 [n]."""
+    u, g = np.empty(n, np.float32), np.empty(n, np.float32)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    check(lib().wa_sample_noise(int(seed) & (2 ** 64 - 1), int(pick), int(id0), int(n), u.ctypes.data_as(f32p),
+                                g.ctypes.data_as(f32p)))
+    return u, g
+
+
+def _sampling_arrays(temperature, seed, n: int):
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (n,)))
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (n,)))
+    return t, s
+
+
+def logits_sample_check(hid, emb, temperature, seed, step: int, histories=None, ts0: int = 0,
+                        max_initial: int = 50, precision: int = wq4.PREC_F16X2):
+    """The sampled form of the fused logits + pick (wa_logits_sample_check) at
+    pick index step + 1: hid cuda f32 [B, D], emb cuda f32 [V, D], temperature
+    / seed per row; histories (each row's sampled tokens so far) selects the
+    timestamp form -> (tokens int32 [B], logprob f32 [B], logits [B, V] the
+    masked rows without noise -- rule f's mask applied here where the kernel
+    reports it -- and mass int32 [B], or None without histories)."""
+    torch = _torch()
+    B, D = hid.shape
+    V = emb.shape[0]
+    t, s = _sampling_arrays(temperature, seed, B)
+    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
+    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
+    mass = torch.zeros(B, device=hid.device, dtype=torch.int32) if rec is not None else None
+    lp = torch.empty(B, device=hid.device, dtype=torch.float32)
+    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32)
+    check(lib().wa_logits_sample_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
+                                       precision, t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                       s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(ts0),
+                                       rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None,
+                                       _ptr(tok), _ptr(lp), _ptr(mass) if mass is not None else None, _ptr(lg)))
+    if mass is not None:
+        lg[mass.bool(), :ts0] = float("-inf")
+    return tok, lp, lg, mass
+
+
+def row_sample_check(logits, temperature, seed, pick: int, suppress_eot: bool = False, histories=None, ts0: int = 0,
+                     max_initial: int = 50):
+    """The stored-logits kernel of the sampled pick (wa_row_sample_check) at
+    pick index `pick`: logits cuda f32 [R, V] -> (tokens int32 [R], logprob f32
+    [R], mass int32 [R]); histories selects the timestamp form."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    t, s = _sampling_arrays(temperature, seed, R)
+    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
+    tok = torch.empty(R, device=logits.device, dtype=torch.int32)
+    mass = torch.empty(R, device=logits.device, dtype=torch.int32)
+    lp = torch.empty(R, device=logits.device, dtype=torch.float32)
+    check(lib().wa_row_sample_check(_dev(logits), _ptr(logits), R, V, 1 if suppress_eot else 0, int(pick),
+                                    t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                    s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(ts0),
+                                    rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None,
+                                    _ptr(tok), _ptr(lp), _ptr(mass)))
+    return tok, lp, mass
+
+
 def _scored_clip(toks, n, lp, ns, lt, lpr) -> dict:
     """One clip of a scored transcribe: lp its max_tokens + 1 log-probability slots."""
     n = int(n)
@@ -600,8 +694,45 @@ class WhisperModel:
         return [self._timestamped(b)
                 for b in self._scored(mels, mels.shape[0], lang_token, max_tokens, eot_stop, max_initial)]
 
+    def transcribe_sampled(self, mel, temperature, seed, lang_token: Optional[int] = 50259, max_tokens: int = 224,
+                           eot_stop: bool = True, timestamps: bool = False, max_initial: int = 50) -> list[dict]:
+        """transcribe with every pick drawn from softmax(z / T) (wa_transcribe_sampled):
+        temperature (finite, >= 0; 0 decodes greedily) and seed per clip, or one
+        value for all.  Per clip the dict of transcribe_scored -- the scores
+        are untempered log-probabilities -- and with timestamps=True that of
+        transcribe_timestamps (segments, seek_frames)."""
+        clips = self._scored(mel, None, lang_token, max_tokens, eot_stop, max_initial,
+                             sampling=(temperature, seed, timestamps))
+        return self._timestamped(clips) if timestamps else clips
+
+    def transcribe_batches_sampled(self, mels, temperature, seed, lang_token: Optional[int] = 50259,
+                                   max_tokens: int = 224, eot_stop: bool = True, timestamps: bool = False,
+                                   max_initial: int = 50) -> list[list[dict]]:
+        """transcribe_batches with sampled picks (wa_transcribe_batches_sampled): mels
+        cuda f32 [NB, B, n_mels, 3000], temperature / seed [NB, B] (or one value
+        for all) -> NB lists of B dicts as transcribe_sampled."""
+        assert mels.dim() == 4
+        out = self._scored(mels, mels.shape[0], lang_token, max_tokens, eot_stop, max_initial,
+                           sampling=(temperature, seed, timestamps))
+        return [self._timestamped(b) for b in out] if timestamps else out
+
+    def transcribe_fallback(self, mel, seed, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+                            logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+                            lang_token: Optional[int] = 50259, max_tokens: int = 224, eot_stop: bool = True,
+                            timestamps: bool = False, max_initial: int = 50) -> list[dict]:
+        """The temperature fallback (wa_transcribe_fallback): decode at
+        temperatures[0]; a clip whose mean log-probability is below
+        logprob_threshold -- unless its no_speech_prob is above
+        no_speech_threshold -- is decoded again at the next temperature, over
+        the same encoder pass.  None switches a threshold off.  Rung r decodes
+        clip c with seed[c] + r.  Per clip the dict of transcribe_sampled of the
+        rung it kept, plus "rung" and "temperature"."""
+        clips = self._scored(mel, None, lang_token, max_tokens, eot_stop, max_initial,
+                             fallback=(temperatures, logprob_threshold, no_speech_threshold, seed, timestamps))
+        return self._timestamped(clips) if timestamps else clips
+
     def _scored(self, mels, NB: Optional[int], lang_token, max_tokens: int, eot_stop: bool,
-                max_initial: Optional[int] = None):
+                max_initial: Optional[int] = None, sampling=None, fallback=None):
         torch = _torch()
         mels = mels.contiguous()
         assert mels.dtype == torch.float32 and mels.is_cuda
@@ -615,7 +746,30 @@ class WhisperModel:
         sc = Scores(lp.ctypes.data_as(f32p), ns.ctypes.data_as(f32p), lt.ctypes.data_as(i32p),
                     lpr.ctypes.data_as(f32p))
         lang = -1 if lang_token is None else int(lang_token)
-        if max_initial is not None:  # the timestamp entries: max_initial before the outputs
+        rung = None
+        if fallback is not None:
+            temps, lp_thr, ns_thr, seed, ts = fallback
+            tl = np.ascontiguousarray(np.asarray(temps, np.float32).reshape(-1))
+            _, sd = _sampling_arrays(0.0, seed, n)
+            nan = float("nan")
+            fb = Fallback(tl.ctypes.data_as(f32p), int(tl.size), nan if lp_thr is None else float(lp_thr),
+                          nan if ns_thr is None else float(ns_thr), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                          1 if ts else 0, int(max_initial))
+            rung = np.zeros(n, np.int32)
+            check(lib().wa_transcribe_fallback(self._h, _ptr(mels), B, lang, max_tokens, 1 if eot_stop else 0,
+                                               ctypes.byref(fb), toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p),
+                                               ctypes.byref(sc), rung.ctypes.data_as(i32p), self._stream()))
+        elif sampling is not None:
+            temperature, seed, ts = sampling
+            flat = lambda a, dt: np.asarray(a, dt).reshape(-1) if np.ndim(a) else a  # [NB, B] arrays: clip-major
+            t, sd = _sampling_arrays(flat(temperature, np.float32), flat(seed, np.uint64), n)
+            sm = Sampling(t.ctypes.data_as(f32p), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), 1 if ts else 0,
+                          int(max_initial))
+            f = lib().wa_transcribe_sampled if NB is None else lib().wa_transcribe_batches_sampled
+            head = (self._h, _ptr(mels)) + ((B,) if NB is None else (NB, B))
+            check(f(*head, lang, max_tokens, 1 if eot_stop else 0, ctypes.byref(sm), toks.ctypes.data_as(i32p),
+                    nt.ctypes.data_as(i32p), ctypes.byref(sc), self._stream()))
+        elif max_initial is not None:  # the timestamp entries: max_initial before the outputs
             f = lib().wa_transcribe_timestamps if NB is None else lib().wa_transcribe_batches_timestamps
             head = (self._h, _ptr(mels)) + ((B,) if NB is None else (NB, B))
             check(f(*head, lang, max_tokens, 1 if eot_stop else 0, int(max_initial), toks.ctypes.data_as(i32p),
@@ -629,6 +783,9 @@ class WhisperModel:
                                                      1 if eot_stop else 0, toks.ctypes.data_as(i32p),
                                                      nt.ctypes.data_as(i32p), ctypes.byref(sc), self._stream()))
         clips = [_scored_clip(toks[i], nt[i], lp[i], ns[i], lt[i], lpr[i]) for i in range(n)]
+        if rung is not None:
+            for c, r in zip(clips, rung):
+                c["rung"], c["temperature"] = int(r), float(tl[r])
         return clips if NB is None else [clips[i * B:(i + 1) * B] for i in range(NB)]
 
     def transcribe_scored(self, mel, lang_token: Optional[int] = 50259, max_tokens: int = 224,
