@@ -1,5 +1,5 @@
 """Temperature sampling on the GPU (wa_transcribe_sampled, wa_transcribe_fallback,
-include/whisper_amd.h): the SAMPLE forms of the fused logits + pick kernel and
+include/whisper_amd.h): the KEYS forms of the fused logits + pick kernel and
 of the stored-logits row kernel, and the model-level paths against a numpy
 driver around the oracle's decoder.  The reference is sample_rules.py (pinned
 by test_sampling.py), composed with ts_rules.py for the timestamp form.
@@ -257,6 +257,44 @@ def test_fused_sampled_timestamp_pick(torch, D, prec):
     for B in (1, 17, 32):
         for step in (0, 5):
             check_fused(torch, D, B, step, prec, True)
+
+
+@pytest.mark.parametrize("V_,ts0", [(300, 200), (300, 256), (1100, 1000)])
+def test_pick_forms_agree_small_vocab(torch, V_, ts0):
+    """The five fused forms are one reduction: at vocabularies of 3 workgroups
+    (fewer than the 8 reduction parts, a padded tail; ts0 inside a workgroup
+    and on a workgroup boundary) and of 9 (uneven parts), D = 128, B in
+    {1, 32}, steps 0 and 5, the sampled check at T = 0 returns the scored
+    check's tokens and log-probabilities, with records the timestamp check's
+    tokens, log-probabilities and mass flags, and the scored check's tokens
+    are the plain check's.  Exact: the forms are compared with each other, so
+    no reference margin enters.  Three rows tie at the maximum across a
+    workgroup boundary and across ts0."""
+    import whisper_amd
+
+    D = 128
+    rng = np.random.default_rng(V_ + ts0)
+    emb = (rng.uniform(-1, 1, (V_, D)) * 0.03).astype(np.float32)
+    q, _ = np.linalg.qr(rng.standard_normal((D, 32)))
+    hid = (q.T * 16.0).astype(np.float32)
+    emb[[5, 133, ts0 - 1, ts0 + 3]] = (q.T.sum(axis=0) * (2.0 / 16.0)).astype(np.float32)
+    text = 7
+    states = [[], [ts0 + 10, text], [ts0 + 10, text, ts0 + 20], [ts0 + 10, text, ts0 + 20, ts0 + 20], [text]]
+    hist = [states[r % 5] for r in range(32)]
+    emb_d = torch.from_numpy(emb).cuda()
+    same = lambda a, b: a.cpu().numpy().tobytes() == b.cpu().numpy().tobytes()
+    for B in (1, 32):
+        h = torch.from_numpy(hid[:B]).cuda()
+        for step in (0, 5):
+            ptok, _ = whisper_amd.logits_argmax_check(h, emb_d, step)
+            stok, slp, _ = whisper_amd.logits_logprob_check(h, emb_d, step)
+            ttok, tlp, _, tmass = whisper_amd.logits_timestamp_check(h, emb_d, hist[:B], step, ts0)
+            tok, lp, _, _ = whisper_amd.logits_sample_check(h, emb_d, 0.0, 11, step)
+            rtok, rlp, _, rmass = whisper_amd.logits_sample_check(h, emb_d, 0.0, 11, step, histories=hist[:B], ts0=ts0)
+            assert same(stok, ptok), (B, step)
+            assert same(tok, stok) and same(lp, slp), (B, step)
+            assert same(rtok, ttok) and same(rlp, tlp) and same(rmass, tmass), (B, step)
+            assert np.isfinite(slp.cpu().numpy()).all() and np.isfinite(tlp.cpu().numpy()).all()
 
 
 @pytest.mark.parametrize("records", [False, True])

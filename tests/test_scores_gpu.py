@@ -8,7 +8,7 @@ Bounds.  u = 2^-24 (f32 unit roundoff).
        f32 logits: |lp - lp64| <= (R + 24) u, R the longest chain of f32
        additions in the reduction as built, 24 for the rounding of v - m on the
        terms that matter, expf, the rescale multiply and logf.
-         fused kernel (pick_from_lds, SCORE = 1): a thread adds its 16 terms
+         fused kernel (pick_from_lds<1, 1, 0>): a thread adds its 16 terms
            to 0 (16 additions), 3 shuffle adds, the last workgroup's thread
            adds ceil(groups / 8) rescaled candidates to 0, 3 shuffle adds:
            R = 22 + ceil(ceil(V / 128) / 8)  (73 at V = 51866, 23 to V = 1024).

@@ -11,14 +11,14 @@ Bounds.  u = 2^-24.
     is compared.
   (i)  a kernel's log-probability against float64 numpy on the kernel's OWN
        masked f32 logits: |lp - lp64| <= (R + 24) u as in test_scores_gpu.py.
-         fused kernel (pick_from_lds_ts): per side a thread adds its 16 terms
+         fused kernel (pick_from_lds<2, 1, 0>): per side a thread adds its 16 terms
            (16 additions), 3 shuffle adds, the last workgroup's thread adds the
            side's rescaled candidates -- ceil(ceil(ts0 / 128) / 8) on the text
            side, the longer one -- and 3 shuffle adds; joining the sides is one
            addition more with a subtract, an expf and a multiply on each term
            (counted as 4): R = 27 + ceil(ceil(ts0 / 128) / 8) = 77 at
            ts0 = 50365.
-         row kernel (row_timestamp_kernel): ceil(ts0 / 256) additions per
+         row kernel (row_pick_kernel<0>): ceil(ts0 / 256) additions per
            thread on the text side, 6 shuffle adds, 3 adds over the waves, the
            join as above: R = 14 + ceil(ts0 / 256) = 211.
   (ii) against the float64 logits: (i) plus twice the logit bound.

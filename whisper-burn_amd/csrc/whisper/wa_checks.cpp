@@ -133,71 +133,74 @@ wq4_status wa_self_attention_check(int device, const float* qkv_dev, float* cach
   });
 }
 
-// wa_logits_argmax_check, with logprob_dev the scored launch of
-// wa_logits_logprob_check, and with rules_host (n_clips records) the
-// timestamp launch of wa_logits_timestamp_check
+// The fused pick on caller data, in the mode the arguments select (PickArgs):
+// wa_logits_argmax_check; with logprob_dev the scored launch of
+// wa_logits_logprob_check; with rules_host (n_clips records) the timestamp
+// launch of wa_logits_timestamp_check; with temperature / seed (host, n_clips
+// each) the sampled launch of wa_logits_sample_check.
 static wq4_status logits_pick_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
                                     int step, wq4_precision prec, int32_t* tok_dev, float* logprob_dev,
                                     float* logits_dev, const TsRule* rules_host = nullptr, int ts0 = 0,
-                                    int32_t* mass_dev = nullptr) {
+                                    int32_t* mass_dev = nullptr, const float* temperature = nullptr,
+                                    const uint64_t* seed = nullptr) {
   const int ns = planes(prec);
   WA_HIP(hipSetDevice(device));
   Dev d;
-  const int64_t erows = emb_tiled_rows(V);
-  const int ng = logits_argmax_groups(V);
-  auto* emb2 = d.alloc<_Float16>((size_t)erows * ns * D);
+  auto* emb2 = d.alloc<_Float16>((size_t)emb_tiled_rows(V) * ns * D);
   auto* st = d.alloc<DecodeState>(1);
-  auto* pval = d.alloc<float>((size_t)32 * ng);
-  auto* pidx = d.alloc<int>((size_t)32 * ng);
-  auto* ctr = d.alloc<int>(1);
-  float* psum = logprob_dev ? d.alloc<float>((size_t)32 * ng) : nullptr;
   const size_t tb = wq4_atiled_bytes(n_clips, D, prec);
   auto* ht = d.alloc<_Float16>(tb / 2);
-  int* ids = nullptr;
-  if (logits_dev) ids = d.alloc<int>((size_t)n_clips * 2 * V);
-  if (!emb2 || !st || !pval || !pidx || !ctr || !ht || (logits_dev && !ids) || (logprob_dev && !psum))
-    return fail(WQ4_ENOMEM, "allocation failed");
-  TsRule* rules = nullptr;
-  float *xval = nullptr, *xsum = nullptr;
-  int* xidx = nullptr;
+  PickArgs p{};
+  p.scratch = d.alloc<float>((size_t)logits_pick_scratch_floats(V));
+  p.counter = d.alloc<int>(1);
+  p.out_tok = tok_dev;
+  p.out_lp = logprob_dev;
+  p.out_mass = mass_dev;
+  p.ts0 = ts0;
+  if (!emb2 || !st || !ht || !p.scratch || !p.counter) return fail(WQ4_ENOMEM, "allocation failed");
   if (rules_host) {
-    rules = d.alloc<TsRule>(n_clips);
-    xval = d.alloc<float>((size_t)32 * ng);
-    xidx = d.alloc<int>((size_t)32 * ng);
-    xsum = d.alloc<float>((size_t)32 * ng);
-    if (!rules || !xval || !xidx || !xsum) return fail(WQ4_ENOMEM, "allocation failed");
+    auto* rules = d.alloc<TsRule>(n_clips);
+    if (!rules) return fail(WQ4_ENOMEM, "allocation failed");
     WA_HIP(hipMemcpy(rules, rules_host, (size_t)n_clips * sizeof(TsRule), hipMemcpyHostToDevice));
+    p.rules = rules;
+  }
+  if (temperature) {
+    auto* temp = d.alloc<float>(n_clips);
+    auto* sd = d.alloc<uint64_t>(n_clips);
+    if (!temp || !sd) return fail(WQ4_ENOMEM, "allocation failed");
+    WA_HIP(hipMemcpy(temp, temperature, (size_t)n_clips * 4, hipMemcpyHostToDevice));
+    WA_HIP(hipMemcpy(sd, seed, (size_t)n_clips * 8, hipMemcpyHostToDevice));
+    p.temp = temp;
+    p.seed = sd;
   }
   WA_HIP(launch_emb_tiled(emb_dev, V, D, ns, emb2, nullptr));
   WA_WQ4(wq4_tile_activations(hid_dev, n_clips, D, D, prec, ht, tb, nullptr));
-  // A trace writes slot state->step + 1 of [clip][2][V] (every id listed at
-  // slot 1): the state's step is then 0 and the EOT suppression of `step`
-  // (step + 1 < 3, whisper.rs:120-122) is passed through min_tokens instead.
-  const DecodeState s0{0, 0, logits_dev ? 0 : step, 0};
-  const int min_tokens = !logits_dev ? kMinTokens : (step + 1 < kMinTokens ? 1 << 30 : 0);
+  // A trace writes slot state->step + 1 of [clip][state->step + 2][V] (every
+  // id listed at that slot).  A sampled pick keeps the caller's step in the
+  // state (its pick index is step + 1); the others trace with step 0, and the
+  // EOT suppression of `step` (step + 1 < 3, whisper.rs:120-122) is passed
+  // through min_tokens instead.
+  const bool fold = logits_dev && !temperature;
+  const DecodeState s0{0, 0, fold ? 0 : step, 0};
+  const int min_tokens = !fold ? kMinTokens : (step + 1 < kMinTokens ? 1 << 30 : 0);
   WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
-  WA_HIP(hipMemset(ctr, 0, sizeof(int)));
+  WA_HIP(hipMemset(p.counter, 0, sizeof(int)));
+  const int s1 = s0.step + 2;
+  int* ids = nullptr;
   float* tr = nullptr;
   if (logits_dev) {
-    std::vector<int> h((size_t)n_clips * 2 * V, 0);
+    ids = d.alloc<int>((size_t)n_clips * s1 * V);
+    tr = d.alloc<float>((size_t)n_clips * s1 * V);
+    if (!ids || !tr) return fail(WQ4_ENOMEM, "allocation failed");
+    std::vector<int> h((size_t)n_clips * s1 * V, 0);
     for (int b = 0; b < n_clips; ++b)
-      for (int v = 0; v < V; ++v) h[((size_t)b * 2 + 1) * V + v] = v;
+      for (int v = 0; v < V; ++v) h[((size_t)b * s1 + s1 - 1) * V + v] = v;
     WA_HIP(hipMemcpy(ids, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-    tr = d.alloc<float>((size_t)n_clips * 2 * V);
-    if (!tr) return fail(WQ4_ENOMEM, "allocation failed");
   }
-  if (rules_host)
-    WA_HIP(launch_logits_argmax_ts(ht, n_clips, D, emb2, ns, V, min_tokens, st, rules, ts0, pval, pidx, psum, xval, xidx,
-                                   xsum, ctr, tok_dev, logprob_dev, mass_dev, ids, tr, 2, V, nullptr, nullptr));
-  else if (logprob_dev)
-    WA_HIP(launch_logits_argmax_scored(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, psum, ctr, tok_dev,
-                                       logprob_dev, ids, tr, 2, V, nullptr, nullptr));
-  else
-    WA_HIP(launch_logits_argmax(ht, n_clips, D, emb2, ns, V, min_tokens, st, pval, pidx, ctr, tok_dev, ids, tr, 2, V,
-                                nullptr, nullptr));
+  WA_HIP(launch_logits_pick(ht, n_clips, D, emb2, ns, V, min_tokens, st, p, ids, tr, s1, V, nullptr, nullptr));
   if (logits_dev)
     for (int b = 0; b < n_clips; ++b)
-      WA_HIP(hipMemcpy(logits_dev + (size_t)b * V, tr + ((size_t)b * 2 + 1) * V, (size_t)V * 4,
+      WA_HIP(hipMemcpy(logits_dev + (size_t)b * V, tr + ((size_t)b * s1 + s1 - 1) * V, (size_t)V * 4,
                        hipMemcpyDeviceToDevice));
   WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
@@ -258,8 +261,8 @@ wq4_status wa_row_timestamp_check(int device, const float* logits_dev, int n_row
   auto* rules = d.alloc<TsRule>(n_rows);
   if (!rules) return fail(WQ4_ENOMEM, "allocation failed");
   WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
-  WA_HIP(launch_row_timestamp(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, tok_dev, logprob_dev,
-                              mass_dev, nullptr, nullptr));
+  WA_HIP(launch_row_pick(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, nullptr, nullptr, 0, tok_dev,
+                         logprob_dev, mass_dev, nullptr, nullptr));
   WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }
@@ -291,7 +294,7 @@ wq4_status wa_timestamp_bookkeep_check(int device, const int32_t* tokens, int n_
   for (int s = 0; s < n_steps; ++s) {  // one token per row and launch, as a decode step feeds them
     for (size_t b = 0; b < B; ++b) col[b] = tokens[b * n_steps + s];
     WA_HIP(hipMemcpy(next, col.data(), B * 4, hipMemcpyHostToDevice));
-    WA_HIP(launch_bookkeep_ts(next, lp, toks, logprob, ntok, done, n_rows, kMaxTokens, 0, st, rules, ts0, V, nullptr));
+    WA_HIP(launch_bookkeep(next, lp, toks, logprob, ntok, done, n_rows, kMaxTokens, 0, st, rules, ts0, V, nullptr));
     WA_HIP(hipMemcpy(records_out + (size_t)s * B * 8, rules, B * sizeof(TsRule), hipMemcpyDeviceToHost));
   }
   return WQ4_OK;
@@ -310,53 +313,8 @@ wq4_status wa_logits_sample_check(int device, const float* hid_dev, const float*
   for (int b = 0; b < n_clips; ++b)
     if (!(temperature[b] >= 0.0f) || !std::isfinite(temperature[b]))
       return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
-  const int ns = planes(prec);
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  const size_t tb = wq4_atiled_bytes(n_clips, D, prec);
-  auto* emb2 = d.alloc<_Float16>((size_t)emb_tiled_rows(V) * ns * D);
-  auto* st = d.alloc<DecodeState>(1);
-  auto* scr = d.alloc<float>((size_t)logits_sample_scratch_floats(V));
-  auto* ctr = d.alloc<int>(1);
-  auto* ht = d.alloc<_Float16>(tb / 2);
-  auto* temp = d.alloc<float>(n_clips);
-  auto* sd = d.alloc<uint64_t>(n_clips);
-  if (!emb2 || !st || !scr || !ctr || !ht || !temp || !sd) return fail(WQ4_ENOMEM, "allocation failed");
-  TsRule* rules = nullptr;
-  if (records) {
-    rules = d.alloc<TsRule>(n_clips);
-    if (!rules) return fail(WQ4_ENOMEM, "allocation failed");
-    WA_HIP(hipMemcpy(rules, records, (size_t)n_clips * sizeof(TsRule), hipMemcpyHostToDevice));
-  }
-  WA_HIP(hipMemcpy(temp, temperature, (size_t)n_clips * 4, hipMemcpyHostToDevice));
-  WA_HIP(hipMemcpy(sd, seed, (size_t)n_clips * 8, hipMemcpyHostToDevice));
-  WA_HIP(launch_emb_tiled(emb_dev, V, D, ns, emb2, nullptr));
-  WA_WQ4(wq4_tile_activations(hid_dev, n_clips, D, D, prec, ht, tb, nullptr));
-  // the state's step is the caller's (the pick index is step + 1); a trace
-  // writes slot step + 1 of [clip][step + 2][V], every id listed there
-  const DecodeState s0{0, 0, step, 0};
-  WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
-  WA_HIP(hipMemset(ctr, 0, sizeof(int)));
-  const int s1 = step + 2;
-  int* ids = nullptr;
-  float* tr = nullptr;
-  if (logits_dev) {
-    ids = d.alloc<int>((size_t)n_clips * s1 * V);
-    tr = d.alloc<float>((size_t)n_clips * s1 * V);
-    if (!ids || !tr) return fail(WQ4_ENOMEM, "allocation failed");
-    std::vector<int> h((size_t)n_clips * s1 * V, 0);
-    for (int b = 0; b < n_clips; ++b)
-      for (int v = 0; v < V; ++v) h[((size_t)b * s1 + step + 1) * V + v] = v;
-    WA_HIP(hipMemcpy(ids, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-  }
-  WA_HIP(launch_logits_argmax_sample(ht, n_clips, D, emb2, ns, V, kMinTokens, st, temp, sd, rules, ts0, scr, ctr,
-                                     tok_dev, logprob_dev, mass_dev, ids, tr, s1, V, nullptr, nullptr));
-  if (logits_dev)
-    for (int b = 0; b < n_clips; ++b)
-      WA_HIP(hipMemcpy(logits_dev + (size_t)b * V, tr + ((size_t)b * s1 + step + 1) * V, (size_t)V * 4,
-                       hipMemcpyDeviceToDevice));
-  WA_HIP(hipDeviceSynchronize());
-  return WQ4_OK;
+  return logits_pick_check(device, hid_dev, emb_dev, n_clips, D, V, step, prec, tok_dev, logprob_dev, logits_dev,
+                           reinterpret_cast<const TsRule*>(records), ts0, mass_dev, temperature, seed);
 }
 
 wq4_status wa_row_sample_check(int device, const float* logits_dev, int n_rows, int V, int suppress_eot, int pick,
@@ -376,8 +334,8 @@ wq4_status wa_row_sample_check(int device, const float* logits_dev, int n_rows, 
   if (records) WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
   WA_HIP(hipMemcpy(temp, temperature, (size_t)n_rows * 4, hipMemcpyHostToDevice));
   WA_HIP(hipMemcpy(sd, seed, (size_t)n_rows * 8, hipMemcpyHostToDevice));
-  WA_HIP(launch_row_sample(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, temp, sd, pick, tok_dev,
-                           logprob_dev, mass_dev, nullptr, nullptr));
+  WA_HIP(launch_row_pick(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, temp, sd, pick, tok_dev,
+                         logprob_dev, mass_dev, nullptr, nullptr));
   WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }

@@ -69,40 +69,48 @@ bool lnfold_on(const wa_model* m, int Tq, const DecodeState* state, int64_t rows
   return true;
 }
 
-// A greedy decode step of <= 32 clips picks its tokens inside the logits
-// kernel (wa::launch_logits_argmax); prompts and larger groups keep the
-// stored logits + separate argmax.
+// A decode step of <= 32 clips picks its tokens inside the logits kernel
+// (wa::launch_logits_pick); prompts and larger groups keep the stored logits +
+// a separate pick.
 bool fused_pick(const DecGroup& g, int Tq, const DecodeState* state) {
   return state != nullptr && Tq == 1 && g.nb <= 32;
 }
 
-// One greedy step (whisper.rs:104-125): bookkeeping, decode_step, argmax.
-// A scored transcribe (m->score) stores each pick's log-probability where its
-// token goes, and a stored-logits group scores its pick with the row kernel.
-// A timestamp transcribe (m->ts) also advances the clips' rule records in its
-// bookkeeping and picks under them (the TS fused launch, or the row kernel).
+// The fused pick of group g in the model's mode: a scored transcribe
+// (m->score) leaves the pick's log-probability in next_lp, a timestamp one
+// (m->ts) picks under the clips' rule records, a sampled one (m->sample) at
+// their temperatures and seeds.
+PickArgs pick_args(const wa_model* m, const DecGroup& g) {
+  PickArgs p{};
+  p.scratch = g.lg_scr;
+  p.counter = g.lg_ctr;
+  p.out_tok = g.next_tok;
+  p.out_lp = m->score ? g.next_lp : nullptr;
+  p.rules = m->ts ? g.ts_rules : nullptr;
+  p.ts0 = m->ts0();
+  p.temp = m->sample ? g.smp_temp : nullptr;
+  p.seed = m->sample ? g.smp_seed : nullptr;
+  return p;
+}
+
+// One greedy step (whisper.rs:104-125): bookkeeping, decode_step, the pick.
+// The bookkeeping stores a scored transcribe's log-probabilities where the
+// tokens go and advances a timestamp transcribe's rule records; a
+// stored-logits group picks with the row kernels, in the mode of pick_args.
 wq4_status decode_step(wa_model* m, DecGroup& g, int eot_stop, hipStream_t st) {
-  if (m->ts)
-    WA_HIP(launch_bookkeep_ts(g.next_tok, g.next_lp, g.tokens, g.logprob, g.ntok, g.done, g.nb, kMaxTokens, eot_stop,
-                              g.state, g.ts_rules, m->ts0(), m->cfg.n_vocab, st));
-  else if (m->score)
-    WA_HIP(launch_bookkeep_scored(g.next_tok, g.next_lp, g.tokens, g.logprob, g.ntok, g.done, g.nb, kMaxTokens,
-                                  eot_stop, g.state, st));
-  else
-    WA_HIP(launch_bookkeep(g.next_tok, g.tokens, g.ntok, g.done, g.nb, kMaxTokens, eot_stop, g.state, st));
+  const PickArgs p = pick_args(m, g);
+  const int V = m->cfg.n_vocab;
+  WA_HIP(launch_bookkeep(g.next_tok, p.out_lp, g.tokens, m->score ? g.logprob : nullptr, g.ntok, g.done, g.nb,
+                         kMaxTokens, eot_stop, g.state, m->ts ? g.ts_rules : nullptr, p.ts0, V, st));
   WA_TRY(decoder_forward(m, g, g.next_tok, 1, g.state, 0, 0, st));
-  if (!fused_pick(g, 1, g.state) && m->sample) {  // the sampled pick over the stored rows, pick step + 1
-    WA_HIP(launch_row_sample(g.logits, g.nb, m->cfg.n_vocab, m->cfg.n_vocab, 0, kMinTokens, g.state,
-                             m->ts ? g.ts_rules : nullptr, m->ts0(), g.smp_temp, g.smp_seed, 0, g.next_tok, g.next_lp,
-                             nullptr, m->range_flag, st));
-  } else if (!fused_pick(g, 1, g.state) && m->ts) {  // the timestamp rule over the stored rows
-    WA_HIP(launch_row_timestamp(g.logits, g.nb, m->cfg.n_vocab, m->cfg.n_vocab, 0, kMinTokens, g.state, g.ts_rules,
-                                m->ts0(), g.next_tok, g.next_lp, nullptr, m->range_flag, st));
-  } else if (!fused_pick(g, 1, g.state)) {
-    WA_HIP(launch_argmax_step(g.logits, g.nb, m->cfg.n_vocab, kMinTokens, g.state, g.next_tok, m->range_flag, st));
+  if (fused_pick(g, 1, g.state)) return WQ4_OK;
+  if (p.temp || p.rules) {  // the sampled (pick step + 1) or timestamp pick over the stored rows
+    WA_HIP(launch_row_pick(g.logits, g.nb, V, V, 0, kMinTokens, g.state, p.rules, p.ts0, p.temp, p.seed, 0, g.next_tok,
+                           g.next_lp, nullptr, m->range_flag, st));
+  } else {
+    WA_HIP(launch_argmax_step(g.logits, g.nb, V, kMinTokens, g.state, g.next_tok, m->range_flag, st));
     if (m->score)
-      WA_HIP(launch_row_logprob(g.logits, g.nb, m->cfg.n_vocab, 0, m->cfg.n_vocab, 0, kMinTokens, g.state, g.next_tok,
-                                1, 0, g.next_lp, 1, st));
+      WA_HIP(launch_row_logprob(g.logits, g.nb, V, 0, V, 0, kMinTokens, g.state, g.next_tok, 1, 0, g.next_lp, 1, st));
   }
   return WQ4_OK;
 }
@@ -173,14 +181,13 @@ wq4_status alloc_activations(wa_model* m) {
     g.atd_ln = tiled(rdec, Dt);
     g.ln_stats = f32(rdec * (Dt / 16) * 2);  // per 16-column tile (the decode-step GEMM)
     g.hid_t = tiled(rdec, Dt);
-    g.lg_val = f32((int64_t)32 * logits_argmax_groups(c.n_vocab));
-    g.lg_idx = d.alloc<int>((size_t)32 * logits_argmax_groups(c.n_vocab));
+    g.lg_scr = f32(logits_pick_scratch_floats(c.n_vocab));
     g.lg_ctr = d.alloc<int>(1);
     m->bytes += (size_t)rdec * m->ns * HP * Dt * 2;
     for (void* p : {(void*)g.xd, (void*)g.qkvd, (void*)g.qd, (void*)g.hid, (void*)g.logits, (void*)g.atd_dec,
                     (void*)g.atf_dec, (void*)g.prompt_tok, (void*)g.next_tok, (void*)g.tokens, (void*)g.ntok,
-                    (void*)g.done, (void*)g.state, (void*)g.xattn_part, (void*)g.xqt, (void*)g.lg_val,
-                    (void*)g.lg_idx, (void*)g.lg_ctr, (void*)g.atd_ln, (void*)g.ln_stats, (void*)g.hid_t,
+                    (void*)g.done, (void*)g.state, (void*)g.xattn_part, (void*)g.xqt, (void*)g.lg_scr,
+                    (void*)g.lg_ctr, (void*)g.atd_ln, (void*)g.ln_stats, (void*)g.hid_t,
                     (void*)g.xkv_part, (void*)g.xkv_ctr})
       if (!p) return fail(WQ4_ENOMEM, "decode-group allocation failed");
     WA_HIP(hipMemset(g.xkv_ctr, 0, (size_t)kvc * c.n_text_head * sizeof(int)));
@@ -445,34 +452,15 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
   }
   // final LN (decoder.rs:286 / 340) and tied-embedding logits of the last
   // position of every clip (decoder.rs:289-292, 342-343)
-  if (fused_pick(g, Tq, state)) {  // decode step: logits + greedy pick in one kernel, into next_tok
+  if (fused_pick(g, Tq, state)) {  // decode step: logits + the mode's pick in one kernel, into next_tok
     // the final LN writes the pick's operand directly (A-tiled, the
     // embedding planes' precision)
     WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, m->prec, g.hid_t, nullptr, st));
     const size_t tofs = (size_t)g.b0 * m->trace_s1 * m->trace_k;
-    if (m->sample)  // the SAMPLE instantiations: the Gumbel-max pick at the rows' temperatures and seeds
-      WA_HIP(launch_logits_argmax_sample(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.smp_temp,
-                                         g.smp_seed, m->ts ? g.ts_rules : nullptr, m->ts0(), g.smp_scr, g.lg_ctr,
-                                         g.next_tok, g.next_lp, nullptr, m->trace_out ? m->trace_ids + tofs : nullptr,
-                                         m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
-                                         m->range_flag, st));
-    else if (m->ts)  // the TS instantiation: the rows' rule records applied, the pick and its log-probability
-      WA_HIP(launch_logits_argmax_ts(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.ts_rules,
-                                     m->ts0(), g.lg_val, g.lg_idx, g.lg_sum, g.lg_xval, g.lg_xidx, g.lg_xsum, g.lg_ctr,
-                                     g.next_tok, g.next_lp, nullptr, m->trace_out ? m->trace_ids + tofs : nullptr,
-                                     m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
-                                     m->range_flag, st));
-    else if (m->score)  // the SCORE = 1 instantiation: the pick's log-probability beside it, into next_lp
-      WA_HIP(launch_logits_argmax_scored(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.lg_val,
-                                         g.lg_idx, g.lg_sum, g.lg_ctr, g.next_tok, g.next_lp,
-                                         m->trace_out ? m->trace_ids + tofs : nullptr,
-                                         m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
-                                         m->range_flag, st));
-    else
-      WA_HIP(launch_logits_argmax(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, g.lg_val, g.lg_idx,
-                                  g.lg_ctr, g.next_tok, m->trace_out ? m->trace_ids + tofs : nullptr,
-                                  m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k,
-                                  m->range_flag, st));
+    WA_HIP(launch_logits_pick(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, pick_args(m, g),
+                              m->trace_out ? m->trace_ids + tofs : nullptr,
+                              m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k, m->range_flag,
+                              st));
     return WQ4_OK;
   }
   WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, WQ4_PREC_F16X2, nullptr, g.hid, st));
@@ -545,8 +533,7 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
     std::vector<int> sot(B, kSOT);
     WA_HIP(hipMemcpyAsync(g.next_tok, sot.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
     WA_TRY(decoder_forward(m, g, g.next_tok, 1, nullptr, 0, 0, st));
-    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 50259, 50259 + c.n_lang, 0, nullptr, g.prompt_tok, plen,
-                         m->range_flag, st));
+    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 50259, 50259 + c.n_lang, 0, g.prompt_tok, plen, m->range_flag, st));
     if (m->score) WA_TRY(score_sot(m, g, g.logits, g.prompt_tok, plen, 0, st));  // before the next pass rewrites g.logits
     // ... then forward_prompt([lang, TRANSCRIBE, NO_TIMESTAMPS]) OVERWRITES the
     // cache from index 0 with positions 0..2 (decoder.rs:272-283) while the
@@ -557,35 +544,28 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
     kv0 = plen;
   }
   if (m->sample) {
-    // the clips' temperatures and seeds, then pick 0 through the sampled row
-    // kernel: under the first pick's rule record (timestamps) or with EOT
-    // suppressed (whisper.rs:97-99)
-    // (pageable: the copies are staged before the calls return)
+    // the clips' temperatures and seeds (pageable: the copies are staged before the calls return)
     WA_HIP(hipMemcpyAsync(g.smp_temp, m->smp_temp + g.clip0, (size_t)B * 4, hipMemcpyHostToDevice, st));
     WA_HIP(hipMemcpyAsync(g.smp_seed, m->smp_seed + g.clip0, (size_t)B * 8, hipMemcpyHostToDevice, st));
-    if (m->ts) {
-      const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, m->ts_max_initial));
-      WA_HIP(hipMemcpyAsync(g.ts_rules, first.data(), (size_t)B * sizeof(TsRule), hipMemcpyHostToDevice, st));
-    }
-    WA_HIP(launch_row_sample(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, m->ts ? g.ts_rules : nullptr, m->ts0(),
-                             g.smp_temp, g.smp_seed, 0, g.next_tok, g.next_lp, nullptr, m->range_flag, st));
-    WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
-  } else if (m->ts) {
-    // every clip's rule record back to the empty history, then the first pick
-    // under it (rule e; EOT is masked with the text) and its log-probability
+  }
+  if (m->ts) {  // every clip's rule record back to the empty history
     const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, m->ts_max_initial));  // pageable: staged
     WA_HIP(hipMemcpyAsync(g.ts_rules, first.data(), (size_t)B * sizeof(TsRule), hipMemcpyHostToDevice, st));
-    WA_HIP(launch_row_timestamp(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, g.ts_rules, m->ts0(), g.next_tok,
-                                g.next_lp, nullptr, m->range_flag, st));
-    WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
+  }
+  if (m->sample || m->ts) {
+    // pick 0 and its log-probability through the row kernel: under the first
+    // pick's rule record (rule e; EOT is masked with the text) or with EOT
+    // suppressed (whisper.rs:97-99)
+    const PickArgs p = pick_args(m, g);
+    WA_HIP(launch_row_pick(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, p.rules, p.ts0, p.temp, p.seed, 0,
+                           g.next_tok, g.next_lp, nullptr, m->range_flag, st));
   } else {
     // first token: EOT suppressed (whisper.rs:97-99)
-    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, nullptr, g.next_tok, 1, m->range_flag, st));
-    if (m->score) {  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
+    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, g.next_tok, 1, m->range_flag, st));
+    if (m->score)  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
       WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st));
-      WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
-    }
   }
+  if (m->score) WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
   // frozen clips start done, and counted: the loop stops once the live ones emitted EOT
   std::vector<int> done0(B, 0);
   int n_frozen = 0;
@@ -709,30 +689,28 @@ wq4_status ensure_ffn_ws(wa_model* m) {
 wq4_status ensure_score_buffers(wa_model* m) {
   if (m->score_alloc_ok) return WQ4_OK;
   const size_t B = (size_t)m->bmax, V = (size_t)m->cfg.n_vocab;
-  const size_t ng = (size_t)32 * logits_argmax_groups(m->cfg.n_vocab);
   bool ok = true;
   for (DecGroup& g : m->groups) {
     g.next_lp = m->dev.alloc<float>(B);
     g.logprob = m->dev.alloc<float>(B * (kMaxTokens + 1));
-    g.lg_sum = m->dev.alloc<float>(ng);
     g.no_speech = m->dev.alloc<float>(B);
     g.lang_prob = m->dev.alloc<float>(B);
     g.lang_tok = m->dev.alloc<int>(B);
     g.z0 = m->dev.alloc<float>(B * V);
-    ok = ok && g.next_lp && g.logprob && g.lg_sum && g.no_speech && g.lang_prob && g.lang_tok && g.z0;
+    ok = ok && g.next_lp && g.logprob && g.no_speech && g.lang_prob && g.lang_tok && g.z0;
   }
   if (!ok) {
     (void)hipGetLastError();  // the failed hipMalloc is handled here
     for (DecGroup& g : m->groups) {
-      for (void* p : {(void*)g.next_lp, (void*)g.logprob, (void*)g.lg_sum, (void*)g.no_speech, (void*)g.lang_prob,
-                      (void*)g.lang_tok, (void*)g.z0})
+      for (void* p : {(void*)g.next_lp, (void*)g.logprob, (void*)g.no_speech, (void*)g.lang_prob, (void*)g.lang_tok,
+                      (void*)g.z0})
         m->dev.release(p);
-      g.next_lp = g.logprob = g.lg_sum = g.no_speech = g.lang_prob = g.z0 = nullptr;
+      g.next_lp = g.logprob = g.no_speech = g.lang_prob = g.z0 = nullptr;
       g.lang_tok = nullptr;
     }
     return fail(WQ4_ENOMEM, "score buffer allocation failed");
   }
-  m->bytes += m->groups.size() * 4 * (B * (kMaxTokens + 1 + 4) + ng + B * V);
+  m->bytes += m->groups.size() * 4 * (B * (kMaxTokens + 1 + 4) + B * V);
   m->score_alloc_ok = true;
   return WQ4_OK;
 }
@@ -742,26 +720,20 @@ wq4_status ensure_score_buffers(wa_model* m) {
 wq4_status ensure_ts_buffers(wa_model* m) {
   if (m->ts_alloc_ok) return WQ4_OK;
   const size_t B = (size_t)m->bmax;
-  const size_t ng = (size_t)32 * logits_argmax_groups(m->cfg.n_vocab);
   bool ok = true;
   for (DecGroup& g : m->groups) {
     g.ts_rules = m->dev.alloc<TsRule>(B);
-    g.lg_xval = m->dev.alloc<float>(ng);
-    g.lg_xidx = m->dev.alloc<int>(ng);
-    g.lg_xsum = m->dev.alloc<float>(ng);
-    ok = ok && g.ts_rules && g.lg_xval && g.lg_xidx && g.lg_xsum;
+    ok = ok && g.ts_rules;
   }
   if (!ok) {
     (void)hipGetLastError();  // the failed hipMalloc is handled here
     for (DecGroup& g : m->groups) {
-      for (void* p : {(void*)g.ts_rules, (void*)g.lg_xval, (void*)g.lg_xidx, (void*)g.lg_xsum}) m->dev.release(p);
+      m->dev.release(g.ts_rules);
       g.ts_rules = nullptr;
-      g.lg_xval = g.lg_xsum = nullptr;
-      g.lg_xidx = nullptr;
     }
     return fail(WQ4_ENOMEM, "timestamp buffer allocation failed");
   }
-  m->bytes += m->groups.size() * (B * sizeof(TsRule) + 3 * ng * 4);
+  m->bytes += m->groups.size() * B * sizeof(TsRule);
   m->ts_alloc_ok = true;
   return WQ4_OK;
 }
@@ -771,24 +743,22 @@ wq4_status ensure_ts_buffers(wa_model* m) {
 wq4_status ensure_sample_buffers(wa_model* m) {
   if (m->sample_alloc_ok) return WQ4_OK;
   const size_t B = (size_t)m->bmax;
-  const size_t nscr = (size_t)logits_sample_scratch_floats(m->cfg.n_vocab);
   bool ok = true;
   for (DecGroup& g : m->groups) {
     g.smp_temp = m->dev.alloc<float>(B);
     g.smp_seed = m->dev.alloc<uint64_t>(B);
-    g.smp_scr = m->dev.alloc<float>(nscr);
-    ok = ok && g.smp_temp && g.smp_seed && g.smp_scr;
+    ok = ok && g.smp_temp && g.smp_seed;
   }
   if (!ok) {
     (void)hipGetLastError();  // the failed hipMalloc is handled here
     for (DecGroup& g : m->groups) {
-      for (void* p : {(void*)g.smp_temp, (void*)g.smp_seed, (void*)g.smp_scr}) m->dev.release(p);
-      g.smp_temp = g.smp_scr = nullptr;
+      for (void* p : {(void*)g.smp_temp, (void*)g.smp_seed}) m->dev.release(p);
+      g.smp_temp = nullptr;
       g.smp_seed = nullptr;
     }
     return fail(WQ4_ENOMEM, "sampling buffer allocation failed");
   }
-  m->bytes += m->groups.size() * (B * 12 + nscr * 4);
+  m->bytes += m->groups.size() * B * 12;
   m->sample_alloc_ok = true;
   return WQ4_OK;
 }

@@ -7,7 +7,7 @@
 //   SDPA             src/model/attention.rs:243-298 (scores / sqrt(64),
 //                    causal mask only when q_len > 1, softmax over keys)
 //   KV-cached decode src/model/attention.rs:93-125, decoder.rs:77-112
-//   logits / argmax  src/model/decoder.rs:289-292, 342-347; whisper.rs:131-138
+// (the logits and the token pick: wa_pick.hip)
 // Every product here is f32 x f32 (v_mfma_f32_32x32x2_f32: exact products,
 // f32 accumulation) or f32 VALU; only the operands handed to the Q4 GEMMs
 // are written in the f16 hi/lo A-tiled layout (wq4_layout.hpp).
@@ -15,20 +15,10 @@
 
 #include <cfloat>
 #include <cstdlib>
-#include <type_traits>
 
 #include "../wq4_device.hpp"
 #include "../wq4_lnmath.hpp"
 #include "wa_kernels.hpp"
-
-// WA_LOGITS_NT (default on): the decode step's 266-MB embedding-table stream
-// (logits_argmax_f16_k32_kernel) with the nontemporal policy, so it does not
-// push the encoder planes the next step's cross-attention re-reads out of the
-// Infinity Cache: decode 928 -> 920 ms at 32 clips, RTF +0.7 % (two A/B runs
-// bracketed by the base build, profiles/r06af_libs.txt, r06ag_libs.txt).
-#ifndef WA_LOGITS_NT
-#define WA_LOGITS_NT 1
-#endif
 
 namespace wa {
 
@@ -36,7 +26,6 @@ using wq4::floatx16;
 using wq4::floatx4;
 using wq4::half8;
 
-constexpr int kEOT = 50257;
 // attention scores scaled by 1/sqrt(64) * log2(e) (attention.rs:262): the
 // softmax runs in base 2, one v_exp_f32 (2^x) per exponential
 constexpr float kEaQScale = 0.125f * 1.4426950408889634f;
@@ -50,9 +39,6 @@ constexpr float kPScale = 16384.0f, kPVInv = 1.0f / (16384.0f * 32.0f);
 constexpr float kEaLazyMax = 1024.0f;  // 1.0 in base-2 units x 2^10 (the scores' operand scale)
 // the conv front-end: input x 2^4, weights x 2^10 (|w| < 64), product x 2^-14
 constexpr float kCvAScale = 16.0f, kCvBScale = 1024.0f, kCvInv = 1.0f / (16.0f * 1024.0f);
-// logits: hidden rows as GEMM activations (x 2^4), the f16-pair table x 2^8
-// (|e| < 255), logits x 2^-12
-constexpr float kEmbScale = 256.0f, kLgInv = 1.0f / (16.0f * 256.0f);
 
 using wq4::kLnMaxV;
 using wq4::wave_sum;
@@ -61,10 +47,6 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
-}
-
-__device__ __forceinline__ floatx16 mfma_f32(float a, float b, const floatx16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
 using wq4::atile_store4;
@@ -901,1442 +883,6 @@ hipError_t launch_embed_fold(const int* tokens, const float* tok_emb, const floa
   else
     hipLaunchKernelGGL(embed_fold_kernel<1>, dim3(B * Tq), dim3(256), 0, st, tokens, tok_emb, pos_emb, Tq, D, state,
                        pos0_host, x, gamma, at, stats);
-  return hipGetLastError();
-}
-
-// -------------------------------------------------------------- logits --
-// logits[b, v] = sum_d h[b, d] E[v, d]; B <= 32 clips per call.  One wave =
-// 32 vocabulary rows; h staged in LDS in 256-wide k chunks.
-__global__ __launch_bounds__(256) void logits_kernel(const float* __restrict__ hid, int B, int D, long ldh,
-                                                     const float* __restrict__ emb, int V,
-                                                     float* __restrict__ logits) {
-  __shared__ float hs[32][256 + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int n = blockIdx.x * 128 + wave * 32 + r;
-  const float* er = emb + (size_t)(n < V ? n : 0) * D;
-  floatx16 acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
-  for (int kc = 0; kc < D; kc += 256) {
-    const int kw = min(256, D - kc);
-    __syncthreads();
-    for (int e = tid; e < 32 * 256; e += 256) {
-      const int row = e >> 8, k = e & 255;
-      hs[row][k] = (row < B && k < kw) ? hid[(size_t)row * ldh + kc + k] : 0.0f;
-    }
-    __syncthreads();
-    for (int k8 = 0; k8 < kw; k8 += 8) {
-      const floatx4 e4 = n < V ? *reinterpret_cast<const floatx4*>(er + kc + k8 + 4 * h) : floatx4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 4; ++s) acc = mfma_f32(hs[r][k8 + 4 * h + s], e4[s], acc);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-    if (row < B && n < V) logits[(size_t)row * V + n] = acc[i];
-  }
-}
-
-hipError_t launch_logits(const float* h, int B, int D, long ldh, const float* emb, int V, float* logits,
-                         hipStream_t st) {
-  for (int b0 = 0; b0 < B; b0 += 32) {
-    const int nb = min(32, B - b0);
-    hipLaunchKernelGGL(logits_kernel, dim3((V + 127) / 128), dim3(256), 0, st, h + (size_t)b0 * ldh, nb, D, ldh,
-                       emb, V, logits + (size_t)b0 * V);
-  }
-  return hipGetLastError();
-}
-
-// -------------------------------------------------------------- argmax --
-// Rust `max_by(partial_cmp)` keeps the LAST of equal maxima (whisper.rs:131-138).
-__device__ __forceinline__ void better(float& bv, int& bi, float v, int i) {
-  if (v > bv || (v == bv && i > bi)) {
-    bv = v;
-    bi = i;
-  }
-}
-
-__global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int V, int lo, int hi,
-                                                     int suppress_fixed, int min_tokens, const DecodeState* state,
-                                                     int* __restrict__ out, int out_stride, int* __restrict__ range_flag) {
-  __shared__ float sv[4];
-  __shared__ int si[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* lg = logits + (size_t)b * V;
-  const int suppress = state ? (state->step + 1 < min_tokens) : suppress_fixed;
-  float bv = -INFINITY;
-  int bi = -1;
-  bool bad = false;
-  for (int i = lo + tid; i < hi; i += 256) {
-    float v = lg[i];
-    bad |= !__builtin_isfinite(v);
-    if (suppress && i == kEOT) v = -INFINITY;
-    better(bv, bi, v, i);
-  }
-  if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(bv, o, 64);
-    const int i = __shfl_xor(bi, o, 64);
-    better(bv, bi, v, i);
-  }
-  if (lane == 0) {
-    sv[wave] = bv;
-    si[wave] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    for (int w = 1; w < 4; ++w) better(bv, bi, sv[w], si[w]);
-    out[(size_t)b * out_stride] = bi < 0 ? lo : bi;
-  }
-}
-
-hipError_t launch_argmax(const float* logits, int B, int V, int lo, int hi, int suppress_eot,
-                         const DecodeState* state, int* out_tok, int out_stride, int* range_flag, hipStream_t st) {
-  hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, V, lo, hi, suppress_eot, 0,
-                     (const DecodeState*)nullptr, out_tok, out_stride, range_flag);
-  (void)state;
-  return hipGetLastError();
-}
-
-hipError_t launch_argmax_step(const float* logits, int B, int V, int min_tokens, const DecodeState* state,
-                              int* out_tok, int* range_flag, hipStream_t st) {
-  hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, V, 0, V, 0, min_tokens, state, out_tok, 1,
-                     range_flag);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------ logits + greedy pick --
-// Decode step (B <= 32 clips): logits[b, v] = h[b] . E[v] (decoder.rs:289-292)
-// fused with the greedy argmax (whisper.rs:119-124, 131-138) -- the logits
-// never reach HBM (logits_argmax_f16_k32_kernel below).  Each workgroup
-// leaves one (max, index) candidate per clip; the last-arriving workgroup
-// (agent-scope ticket, write-through partials: cdna_hip_programming.md
-// Guideline 16 R1) reduces them.  (value, index) is compared
-// lexicographically -- the largest value, the LARGEST index among equal
-// maxima -- so the result equals the sequential Rust max_by scan whatever the
-// reduction order.
-
-__device__ __forceinline__ void better_pair(float& bv, int& bi, float v, int i) {
-  if (v > bv || (v == bv && i > bi)) {
-    bv = v;
-    bi = i;
-  }
-}
-
-// Greedy pick of a workgroup's 32 x 128 logits block lg[clip][kLgPickLd]
-// (already masked), then the last-arriving workgroup's pick over all
-// workgroups' candidates.
-// SCORE = 1 (scored transcribes) also leaves the pick's log-probability
-// lp = z[tok] - logsumexp(z) = -log(sum_v exp(z[v] - M)), M = z[tok] the row
-// maximum, in out_lp[clip]: each workgroup adds, beside its candidate
-// (m_w, index), s_w = sum exp(z - m_w) over its 128 logits (psum, a third
-// [32][groups] scratch array, the same write-through stores ahead of the
-// ticket), and the last-arriving workgroup, which knows M, sums
-// S = sum_w s_w exp(m_w - M) and writes -log S.  A masked (-inf) logit adds
-// 0; two equal maxima add 1 each.  f32 throughout; the longest chain of
-// additions is 16 per thread + 3 shuffles + ceil(groups / 8) candidates + 3
-// shuffles (73 at V = 51866).  SCORE = 0 is the pick alone.
-constexpr int kLgPickLd = 132;
-template <int SCORE>
-__device__ __forceinline__ void pick_from_lds(const float* lg, int B, int V, float* __restrict__ pval,
-                                              int* __restrict__ pidx, float* __restrict__ psum,
-                                              int* __restrict__ counter, int* __restrict__ out_tok,
-                                              float* __restrict__ out_lp, int* ticket) {
-  const int tid = threadIdx.x, nwg = gridDim.x;
-  __syncthreads();
-  const int row = tid >> 3, part = tid & 7;
-  float bv = -INFINITY;
-  int bi = -1;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int c = part * 16 + j;
-    const int idx = blockIdx.x * 128 + c;
-    if (idx < V) better_pair(bv, bi, lg[row * kLgPickLd + c], idx);
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    const float v2 = __shfl_xor(bv, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    better_pair(bv, bi, v2, i2);
-  }
-  const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(pval, 0, 32 * nwg * 4, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(pidx, 0, 32 * nwg * 4, 0x00020000);
-  __amdgpu_buffer_rsrc_t rs = rv;
-  if constexpr (SCORE) {
-    // s_w over this workgroup's logits of the row, relative to its maximum
-    // bv (the same in the row's 8 threads); every logit masked: 0
-    float s = 0.0f;
-    if (bv > -INFINITY) {
-#pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int c = part * 16 + j;
-        if (blockIdx.x * 128 + c < V) s += expf(lg[row * kLgPickLd + c] - bv);
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) s += __shfl_xor(s, o, 64);
-    rs = __builtin_amdgcn_make_buffer_rsrc(psum, 0, 32 * nwg * 4, 0x00020000);
-    if (part == 0 && row < B)
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s), rs,
-                                            (uint32_t)(row * nwg + blockIdx.x) * 4, 0, 16);  // sc1
-  }
-  if (part == 0 && row < B) {
-    const uint32_t off = (uint32_t)(row * nwg + blockIdx.x) * 4;
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, bv), rv, off, 0, 16);  // sc1
-    __builtin_amdgcn_raw_buffer_store_b32((uint32_t)bi, ri, off, 0, 16);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    typedef __attribute__((address_space(1))) int gint;
-    const int prev = __hip_atomic_fetch_add((gint*)counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *ticket = prev == nwg - 1;
-  }
-  __syncthreads();
-  if (!*ticket) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler-only: loads stay below the ticket
-  bv = -INFINITY;
-  bi = -1;
-  if (row < B) {
-    for (int j = part; j < nwg; j += 8) {
-      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-      const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, off, 0, 16));
-      const int i = (int)__builtin_amdgcn_raw_buffer_load_b32(ri, off, 0, 16);
-      better_pair(bv, bi, v, i);
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    const float v2 = __shfl_xor(bv, o, 64);
-    const int i2 = __shfl_xor(bi, o, 64);
-    better_pair(bv, bi, v2, i2);
-  }
-  if (part == 0 && row < B) out_tok[row] = bi < 0 ? 0 : bi;
-  if constexpr (SCORE) {
-    // bv = M in the row's 8 threads: the candidates again, rescaled to it
-    float S = 0.0f;
-    if (row < B && bv > -INFINITY) {
-      for (int j = part; j < nwg; j += 8) {
-        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-        const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rv, off, 0, 16));
-        const float s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 16));
-        S += s * expf(v - bv);
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < 8; o <<= 1) S += __shfl_xor(S, o, 64);
-    if (part == 0 && row < B) out_lp[row] = -logf(S);
-  }
-  if (tid == 0) {
-    typedef __attribute__((address_space(1))) int gint;
-    __hip_atomic_store((gint*)counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-  }
-}
-
-// ------------------------------------------------- timestamp rules --
-// The rule record's history update (TsRule, wa_kernels.hpp): the one
-// statement of rules c and d, shared by the bookkeeping kernel and the host.
-__host__ __device__ inline TsRule ts_rule_step(const TsRule& r, int tok, int ts0, int V) {
-  TsRule n;
-  n.first = 0;
-  n.penult = (r.first || r.last) ? 1 : 0;
-  n.last = tok >= ts0 ? 1 : 0;
-  n.t_last = n.last ? tok : r.t_last;
-  n.ts_hi = V - 1;
-  if (n.last && n.penult) {  // a closed pair (or a lone first timestamp): text next, no timestamp
-    n.text_ok = 1;
-    n.ts_lo = V;
-  } else if (n.last) {  // text then a timestamp: its partner (>= it) or EOT
-    n.text_ok = 0;
-    n.ts_lo = n.t_last;
-  } else {  // text: more text, or a timestamp past the last one
-    n.text_ok = 1;
-    n.ts_lo = n.t_last >= 0 ? n.t_last + 1 : ts0;
-  }
-  n.pad = 0;
-  return n;
-}
-
-TsRule ts_rule_first(int ts0, int V, int max_initial) {
-  TsRule r{};
-  r.text_ok = 0;
-  r.ts_lo = ts0;
-  r.ts_hi = max_initial < 0 ? V - 1 : (int)std::min<int64_t>(V - 1, (int64_t)ts0 + max_initial);
-  r.first = 1;
-  r.last = 0;
-  r.penult = 1;
-  r.t_last = -1;
-  return r;
-}
-
-TsRule ts_rule_next(const TsRule& r, int tok, int ts0, int V) { return ts_rule_step(r, tok, ts0, V); }
-
-// Masks a-e for one id of a row: r = the record's (text_ok, ts_lo, ts_hi,
-// first).  The one statement of the masks, shared by the fused and the
-// stored-logits pick.
-__device__ __forceinline__ bool ts_masked(int id, int ts0, const int4& r, bool suppress_eot) {
-  if (id >= ts0) return id < r.y || id > r.z;        // timestamps: the allowed range only (c, d, e)
-  if (id > kEOT) return true;                         // the specials (b)
-  if (id == kEOT) return suppress_eot || r.w != 0;    // a, and the first pick (e)
-  return r.x == 0;                                    // text (c, e)
-}
-
-// The mass rule and the pick from a row's two sides: (mt, it) the best text
-// candidate with st = sum exp(z - mt) over the text side, (mx, ix, sx) the
-// same over the timestamps; a side with nothing allowed is (-inf, -1, 0).
-// lp = the pick's log-probability over the sides that survive.
-__device__ __forceinline__ void ts_decide(float mt, int it, float st, float mx, int ix, float sx, int& tok, float& lp,
-                                          int& mass) {
-  const float lse_x = mx > -INFINITY ? mx + logf(sx) : -INFINITY;
-  mass = lse_x > mt ? 1 : 0;  // rule f: raw logits, the softmax normaliser is common to both sides
-  if (mass) {
-    tok = ix;
-    lp = -logf(sx);
-  } else {
-    float M = mt;
-    tok = it;
-    better_pair(M, tok, mx, ix);
-    const float a = mt > -INFINITY ? st * expf(mt - M) : 0.0f;
-    const float b = mx > -INFINITY ? sx * expf(mx - M) : 0.0f;
-    lp = -logf(a + b);
-  }
-  if (tok < 0) tok = 0;
-}
-
-// What the timestamp instantiation of the fused kernel takes beside the
-// scored form's arguments (unused, and never read, by the others).
-struct TsArgs {
-  const TsRule* rules;
-  int ts0;
-  float* xval;
-  int* xidx;
-  float* xsum;
-  int* out_mass;
-};
-
-// pick_from_lds of a timestamp decode: each workgroup leaves per row a text
-// candidate with its exp sum (pval / pidx / psum; workgroups that hold an id
-// below ts0) and a timestamp candidate with its own (xval / xidx / xsum;
-// workgroups that hold an id from ts0 on -- the workgroup ts0 falls in
-// leaves both), the same write-through stores ahead of the ticket; the
-// last-arriving workgroup merges each side, applies the mass rule and picks
-// (ts_decide).  f32 throughout; the longest chain of additions on the text
-// side is 16 per thread + 3 shuffles + ceil(ceil(ts0 / 128) / 8) candidates +
-// 3 shuffles, and one more to join the sides (73 at ts0 = 50365).
-__device__ __forceinline__ void pick_from_lds_ts(const float* lg, int B, int V, const TsArgs& ts,
-                                                 float* __restrict__ pval, int* __restrict__ pidx,
-                                                 float* __restrict__ psum, int* __restrict__ counter,
-                                                 int* __restrict__ out_tok, float* __restrict__ out_lp, int* ticket) {
-  const int tid = threadIdx.x, nwg = gridDim.x;
-  const int ts0 = ts.ts0;
-  const int nT = min(nwg, (ts0 + 127) / 128);  // workgroups [0, nT) hold text ids
-  const int jx0 = min(nwg, ts0 / 128);         // workgroups [jx0, nwg) hold timestamp ids
-  const bool has_t = (int)blockIdx.x < nT, has_x = (int)blockIdx.x >= jx0;
-  __syncthreads();
-  const int row = tid >> 3, part = tid & 7;
-  float tv = -INFINITY, xv = -INFINITY;
-  int ti = -1, xi = -1;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int c = part * 16 + j;
-    const int idx = blockIdx.x * 128 + c;
-    const float v = lg[row * kLgPickLd + c];
-    if (idx < V) {
-      if (idx < ts0)
-        better_pair(tv, ti, v, idx);
-      else
-        better_pair(xv, xi, v, idx);
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    const float v2 = __shfl_xor(tv, o, 64), v3 = __shfl_xor(xv, o, 64);
-    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
-    better_pair(tv, ti, v2, i2);
-    better_pair(xv, xi, v3, i3);
-  }
-  // each side's sum relative to its own maximum; a side with every logit masked: 0
-  float s_t = 0.0f, s_x = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int c = part * 16 + j;
-    const int idx = blockIdx.x * 128 + c;
-    const float v = lg[row * kLgPickLd + c];
-    if (idx < V) {
-      if (idx < ts0) {
-        if (tv > -INFINITY) s_t += expf(v - tv);
-      } else {
-        if (xv > -INFINITY) s_x += expf(v - xv);
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    s_t += __shfl_xor(s_t, o, 64);
-    s_x += __shfl_xor(s_x, o, 64);
-  }
-  const uint32_t bytes = 32 * nwg * 4;
-  const __amdgpu_buffer_rsrc_t rtv = __builtin_amdgcn_make_buffer_rsrc(pval, 0, bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rti = __builtin_amdgcn_make_buffer_rsrc(pidx, 0, bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rts = __builtin_amdgcn_make_buffer_rsrc(psum, 0, bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxv = __builtin_amdgcn_make_buffer_rsrc(ts.xval, 0, bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxi = __builtin_amdgcn_make_buffer_rsrc(ts.xidx, 0, bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rxs = __builtin_amdgcn_make_buffer_rsrc(ts.xsum, 0, bytes, 0x00020000);
-  if (part == 0 && row < B) {
-    const uint32_t off = (uint32_t)(row * nwg + blockIdx.x) * 4;  // < bytes: row < 32, blockIdx.x < nwg
-    if (has_t) {
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, tv), rtv, off, 0, 16);  // sc1
-      __builtin_amdgcn_raw_buffer_store_b32((uint32_t)ti, rti, off, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s_t), rts, off, 0, 16);
-    }
-    if (has_x) {
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, xv), rxv, off, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b32((uint32_t)xi, rxi, off, 0, 16);
-      __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, s_x), rxs, off, 0, 16);
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    typedef __attribute__((address_space(1))) int gint;
-    const int prev = __hip_atomic_fetch_add((gint*)counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *ticket = prev == nwg - 1;
-  }
-  __syncthreads();
-  if (!*ticket) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler-only: loads stay below the ticket
-  tv = xv = -INFINITY;
-  ti = xi = -1;
-  if (row < B) {
-    for (int j = part; j < nT; j += 8) {
-      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-      const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rtv, off, 0, 16));
-      const int i = (int)__builtin_amdgcn_raw_buffer_load_b32(rti, off, 0, 16);
-      better_pair(tv, ti, v, i);
-    }
-    for (int j = jx0 + part; j < nwg; j += 8) {
-      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-      const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxv, off, 0, 16));
-      const int i = (int)__builtin_amdgcn_raw_buffer_load_b32(rxi, off, 0, 16);
-      better_pair(xv, xi, v, i);
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    const float v2 = __shfl_xor(tv, o, 64), v3 = __shfl_xor(xv, o, 64);
-    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
-    better_pair(tv, ti, v2, i2);
-    better_pair(xv, xi, v3, i3);
-  }
-  // tv = M_text, xv = M_ts in the row's 8 threads: the candidates again, rescaled to them
-  float S_t = 0.0f, S_x = 0.0f;
-  if (row < B) {
-    if (tv > -INFINITY)
-      for (int j = part; j < nT; j += 8) {
-        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-        const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rtv, off, 0, 16));
-        const float s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rts, off, 0, 16));
-        S_t += s * expf(v - tv);
-      }
-    if (xv > -INFINITY)
-      for (int j = jx0 + part; j < nwg; j += 8) {
-        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-        const float v = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxv, off, 0, 16));
-        const float s = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rxs, off, 0, 16));
-        S_x += s * expf(v - xv);
-      }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    S_t += __shfl_xor(S_t, o, 64);
-    S_x += __shfl_xor(S_x, o, 64);
-  }
-  if (part == 0 && row < B) {
-    int tok, mass;
-    float lp;
-    ts_decide(tv, ti, S_t, xv, xi, S_x, tok, lp, mass);
-    out_tok[row] = tok;
-    out_lp[row] = lp;
-    if (ts.out_mass) ts.out_mass[row] = mass;
-  }
-  if (tid == 0) {
-    typedef __attribute__((address_space(1))) int gint;
-    __hip_atomic_store((gint*)counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-  }
-}
-
-// ------------------------------------------------ temperature sampling --
-// Gumbel-max: argmax_v (z_v + T g_v), g i.i.d. standard Gumbel, is a draw
-// from softmax(z / T) -- the pick stays an argmax, over perturbed keys.  The
-// noise is a pure function of (clip seed, pick index, token id): splitmix64's
-// finaliser over a per-pick key, 23 bits to a uniform strictly inside (0, 1)
-// (exact in f32), g = -log(-log u) in [-2.82, 16.64].  The one definition,
-// shared by the fused kernel, the row kernel and the host (sample_noise).
-__host__ __device__ inline uint64_t smp_mix(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-__host__ __device__ inline uint64_t smp_pick_key(uint64_t seed, int pick) {
-  return smp_mix(seed + 0x9E3779B97F4A7C15ull * (uint64_t)(pick + 1));
-}
-__host__ __device__ inline float smp_uniform(uint64_t k, int v) {
-  const uint32_t h = (uint32_t)(smp_mix(k ^ (uint64_t)v) >> 41);  // 23 bits
-  return ((float)h + 0.5f) * 0x1p-23f;                            // exact: 2 h + 1 < 2^24
-}
-__host__ __device__ inline float smp_gumbel(uint64_t k, int v) { return -logf(-logf(smp_uniform(k, v))); }
-// The key of logit z: a clip with T = 0 evaluates no noise; -inf stays -inf (g is finite).
-__device__ __forceinline__ float smp_key(float z, float T, uint64_t k, int v) {
-  return T > 0.0f ? fmaf(T, smp_gumbel(k, v), z) : z;
-}
-
-void sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out) {
-  const uint64_t k = smp_pick_key(seed, pick);
-  for (int i = 0; i < n; ++i) {
-    if (u_out) u_out[i] = smp_uniform(k, id0 + i);
-    if (g_out) g_out[i] = smp_gumbel(k, id0 + i);
-  }
-}
-
-// (key, index) as better_pair, carrying the raw logit at the index.
-__device__ __forceinline__ void better_key(float& bk, int& bi, float& bz, float k, int i, float z) {
-  if (k > bk || (k == bk && i > bi)) {
-    bk = k;
-    bi = i;
-    bz = z;
-  }
-}
-
-// What a sampled instantiation of the fused kernel takes beside TsArgs: the
-// clips' temperatures and seeds (read at run time, not baked into the graph)
-// and one scratch block scr [side][5][32][groups] f32 -- per side (0 text or
-// the whole row, 1 timestamps) the workgroups' key candidates (key, index,
-// raw logit there), raw maxima and exp sums relative to them.
-struct SampleArgs : TsArgs {
-  const float* temp;
-  const uint64_t* seed;
-  float* scr;
-};
-enum { kSmpKey = 0, kSmpIdx = 1, kSmpZ = 2, kSmpMax = 3, kSmpSum = 4, kSmpArrays = 5 };
-
-// pick_from_lds / pick_from_lds_ts of a sampled decode: each workgroup leaves
-// per row (and, TS, per side) its best key with the raw logit at it, its raw
-// maximum m_w and s_w = sum exp(z - m_w) -- the sums exactly as the unsampled
-// forms add them, so a T = 0 row repeats their bits -- and the last-arriving
-// workgroup merges M = max m_w, S = sum s_w exp(m_w - M), decides rule f from
-// the raw sums (TS; the noise never reaches it), picks the best key over the
-// surviving side(s) and writes lp = z_tok - M - log S, the untempered
-// log-probability.  The pick key k(seed, pick) is hashed once per thread.
-template <int TS>
-__device__ __forceinline__ void pick_from_lds_sample(const float* lg, int B, int V, int pick, const SampleArgs& a,
-                                                     int* __restrict__ counter, int* __restrict__ out_tok,
-                                                     float* __restrict__ out_lp, int* ticket) {
-  const int tid = threadIdx.x, nwg = gridDim.x;
-  const int ts0 = TS ? a.ts0 : V;              // plain rows: one side, every id on it
-  const int nT = min(nwg, (ts0 + 127) / 128);  // workgroups [0, nT) hold side-0 ids
-  const int jx0 = min(nwg, ts0 / 128);         // workgroups [jx0, nwg) hold side-1 ids
-  const bool has_t = (int)blockIdx.x < nT, has_x = TS && (int)blockIdx.x >= jx0;
-  __syncthreads();
-  const int row = tid >> 3, part = tid & 7;
-  const float T = row < B ? a.temp[row] : 0.0f;  // rows >= B: no noise
-  const uint64_t k = T > 0.0f ? smp_pick_key(a.seed[row], pick) : 0;
-  float tm = -INFINITY, xm = -INFINITY;                                    // raw maxima
-  float tk = -INFINITY, xk = -INFINITY, tz = -INFINITY, xz = -INFINITY;  // key candidates
-  int ti = -1, xi = -1;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int c = part * 16 + j;
-    const int idx = blockIdx.x * 128 + c;
-    const float z = lg[row * kLgPickLd + c];
-    if (idx < V) {
-      const float key = smp_key(z, T, k, idx);
-      if (!TS || idx < ts0) {
-        tm = fmaxf(tm, z);
-        better_key(tk, ti, tz, key, idx, z);
-      } else {
-        xm = fmaxf(xm, z);
-        better_key(xk, xi, xz, key, idx, z);
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    tm = fmaxf(tm, __shfl_xor(tm, o, 64));
-    const float k2 = __shfl_xor(tk, o, 64), z2 = __shfl_xor(tz, o, 64);
-    const int i2 = __shfl_xor(ti, o, 64);
-    better_key(tk, ti, tz, k2, i2, z2);
-    if constexpr (TS) {
-      xm = fmaxf(xm, __shfl_xor(xm, o, 64));
-      const float k3 = __shfl_xor(xk, o, 64), z3 = __shfl_xor(xz, o, 64);
-      const int i3 = __shfl_xor(xi, o, 64);
-      better_key(xk, xi, xz, k3, i3, z3);
-    }
-  }
-  // each side's sum relative to its own raw maximum; a side with every logit masked: 0
-  float s_t = 0.0f, s_x = 0.0f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    const int c = part * 16 + j;
-    const int idx = blockIdx.x * 128 + c;
-    const float v = lg[row * kLgPickLd + c];
-    if (idx < V) {
-      if (!TS || idx < ts0) {
-        if (tm > -INFINITY) s_t += expf(v - tm);
-      } else {
-        if (xm > -INFINITY) s_x += expf(v - xm);
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    s_t += __shfl_xor(s_t, o, 64);
-    if constexpr (TS) s_x += __shfl_xor(s_x, o, 64);
-  }
-  const uint32_t plane = 32u * nwg * 4u;  // bytes of one [32][groups] array
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(a.scr, 0, (TS ? 2 : 1) * kSmpArrays * plane, 0x00020000);
-  auto put = [&](int side, int arr, uint32_t off, uint32_t bits) {
-    __builtin_amdgcn_raw_buffer_store_b32(bits, rs, (uint32_t)(side * kSmpArrays + arr) * plane + off, 0, 16);  // sc1
-  };
-  auto get = [&](int side, int arr, uint32_t off) {
-    return __builtin_amdgcn_raw_buffer_load_b32(rs, (uint32_t)(side * kSmpArrays + arr) * plane + off, 0, 16);
-  };
-  auto f2u = [](float f) { return __builtin_bit_cast(uint32_t, f); };
-  auto u2f = [](uint32_t u) { return __builtin_bit_cast(float, u); };
-  if (part == 0 && row < B) {
-    const uint32_t off = (uint32_t)(row * nwg + blockIdx.x) * 4;  // < plane: row < 32, blockIdx.x < nwg
-    if (has_t) {
-      put(0, kSmpKey, off, f2u(tk));
-      put(0, kSmpIdx, off, (uint32_t)ti);
-      put(0, kSmpZ, off, f2u(tz));
-      put(0, kSmpMax, off, f2u(tm));
-      put(0, kSmpSum, off, f2u(s_t));
-    }
-    if (has_x) {
-      put(1, kSmpKey, off, f2u(xk));
-      put(1, kSmpIdx, off, (uint32_t)xi);
-      put(1, kSmpZ, off, f2u(xz));
-      put(1, kSmpMax, off, f2u(xm));
-      put(1, kSmpSum, off, f2u(s_x));
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    typedef __attribute__((address_space(1))) int gint;
-    const int prev = __hip_atomic_fetch_add((gint*)counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *ticket = prev == nwg - 1;
-  }
-  __syncthreads();
-  if (!*ticket) return;
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // compiler-only: loads stay below the ticket
-  tm = xm = tk = xk = tz = xz = -INFINITY;
-  ti = xi = -1;
-  if (row < B) {
-    for (int j = part; j < nT; j += 8) {
-      const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-      tm = fmaxf(tm, u2f(get(0, kSmpMax, off)));
-      better_key(tk, ti, tz, u2f(get(0, kSmpKey, off)), (int)get(0, kSmpIdx, off), u2f(get(0, kSmpZ, off)));
-    }
-    if constexpr (TS)
-      for (int j = jx0 + part; j < nwg; j += 8) {
-        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-        xm = fmaxf(xm, u2f(get(1, kSmpMax, off)));
-        better_key(xk, xi, xz, u2f(get(1, kSmpKey, off)), (int)get(1, kSmpIdx, off), u2f(get(1, kSmpZ, off)));
-      }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    tm = fmaxf(tm, __shfl_xor(tm, o, 64));
-    const float k2 = __shfl_xor(tk, o, 64), z2 = __shfl_xor(tz, o, 64);
-    const int i2 = __shfl_xor(ti, o, 64);
-    better_key(tk, ti, tz, k2, i2, z2);
-    if constexpr (TS) {
-      xm = fmaxf(xm, __shfl_xor(xm, o, 64));
-      const float k3 = __shfl_xor(xk, o, 64), z3 = __shfl_xor(xz, o, 64);
-      const int i3 = __shfl_xor(xi, o, 64);
-      better_key(xk, xi, xz, k3, i3, z3);
-    }
-  }
-  // tm = M (M_text), xm = M_ts in the row's 8 threads: the sums again, rescaled to them
-  float S_t = 0.0f, S_x = 0.0f;
-  if (row < B) {
-    if (tm > -INFINITY)
-      for (int j = part; j < nT; j += 8) {
-        const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-        S_t += u2f(get(0, kSmpSum, off)) * expf(u2f(get(0, kSmpMax, off)) - tm);
-      }
-    if constexpr (TS)
-      if (xm > -INFINITY)
-        for (int j = jx0 + part; j < nwg; j += 8) {
-          const uint32_t off = (uint32_t)(row * nwg + j) * 4;
-          S_x += u2f(get(1, kSmpSum, off)) * expf(u2f(get(1, kSmpMax, off)) - xm);
-        }
-  }
-#pragma unroll
-  for (int o = 1; o < 8; o <<= 1) {
-    S_t += __shfl_xor(S_t, o, 64);
-    if constexpr (TS) S_x += __shfl_xor(S_x, o, 64);
-  }
-  if (part == 0 && row < B) {
-    // lpg = -log sum exp(z - Ms) over the surviving side(s), Ms their raw
-    // maximum, as the unsampled forms write it; the sampled token is d = z_tok
-    // - Ms below that (d = 0: the greedy token, their bits)
-    int tok = ti, mass = 0;
-    float lpg, Ms = tm, zt = tz;
-    if constexpr (TS) {
-      int unused;
-      ts_decide(tm, 0, S_t, xm, 0, S_x, unused, lpg, mass);
-      if (mass) {
-        Ms = xm;
-        tok = xi;
-        zt = xz;
-      } else {
-        Ms = fmaxf(tm, xm);
-        better_key(tk, tok, zt, xk, xi, xz);
-      }
-      if (a.out_mass) a.out_mass[row] = mass;
-    } else {
-      lpg = -logf(S_t);
-    }
-    const float d = zt - Ms;
-    out_tok[row] = tok < 0 ? 0 : tok;
-    out_lp[row] = d == 0.0f ? lpg : d + lpg;
-  }
-  if (tid == 0) {
-    typedef __attribute__((address_space(1))) int gint;
-    __hip_atomic_store((gint*)counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-  }
-}
-
-constexpr int kLg2Chunk = 128;
-// 16-row groups of the fragment-tiled table (V padded to 128-row workgroups)
-__host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 127) / 128 * 8; }
-
-// Tied-embedding logits of the decode step on f16 MFMA, fused with the greedy
-// pick: the embedding as exact-to-2^-22 f16 pairs E = hi + lo in a
-// fragment-tiled table (launch_emb_tiled: a lane's fragment is 8 dims of one
-// of 16 rows, one load instruction reads 1 KiB contiguous), the hidden rows
-// as the A-tiled f16-pair operand the final LayerNorm writes (wq4_layernorm,
-// the same split as the GEMMs); three 16x16x32 f16 MFMAs per product
-// (hi*hi + lo*hi + hi*lo), f32 accumulation.  Wave = 32 vocabulary rows as
-// two 16-row m-tiles, the 32 clips as two n-tiles.  Per 128-dim chunk the
-// hidden fragments (32 rows x 128 dims, 8 or 16 KiB) come into an LDS double
-// buffer through registers one chunk ahead, beside the next chunk's table
-// fragments in registers: one barrier per chunk, no conversion.  trace_out
-// (diagnostics, null in the product graph): the logits of
-// trace_ids[clip][step + 1][0..trace_k) are written to the same slots of
-// trace_out, as the pick sees them (EOT already masked).
-// TS = 1 (timestamp transcribes): the masks of the rows' rule records
-// (ts_masked) while lg[] is written, and pick_from_lds_ts; `ts` is read by
-// that instantiation only.
-// SAMPLE = 1 (sampled transcribes, with SCORE; with or without TS): the pick
-// is pick_from_lds_sample over Gumbel-perturbed keys at pick index
-// state->step + 1; its arguments ride behind TsArgs (SampleArgs), so the
-// other instantiations keep their argument lists.
-template <int NS, int SCORE = 0, int TS = 0, int SAMPLE = 0>
-__global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
-    const _Float16* __restrict__ htiled, int B, int D, const _Float16* __restrict__ emb2, int V, int min_tokens,
-    const DecodeState* __restrict__ state, float* __restrict__ pval, int* __restrict__ pidx, int* __restrict__ counter,
-    int* __restrict__ out_tok, const int* __restrict__ trace_ids, float* __restrict__ trace_out, int trace_s1,
-    int trace_k, int* __restrict__ range_flag, float* __restrict__ psum, float* __restrict__ out_lp,
-    std::conditional_t<SAMPLE != 0, SampleArgs, TsArgs> ts) {
-  constexpr int KS = kLg2Chunk / 32;             // Q4-block-sized k-steps per chunk
-  constexpr int HCH = KS * 2 * NS * 1024;        // bytes of hidden fragments per chunk
-  static_assert(HCH % (256 * 16) == 0, "whole glds rounds");
-  __shared__ __attribute__((aligned(16))) uint8_t smem[2 * HCH + 32 * kLgPickLd * 4 + 16];
-  float* lg = reinterpret_cast<float*>(smem + 2 * HCH);
-  int* ticket = reinterpret_cast<int*>(smem + 2 * HCH + 32 * kLgPickLd * 4);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l16 = lane & 15, lq = lane >> 4;
-  const int v0 = blockIdx.x * 128 + wave * 32;
-  // chunk-major table (launch_emb_tiled): this wave's two 16-row groups are
-  // 2 KS NS KiB contiguous per chunk, and a chunk of the whole table is one
-  // contiguous stretch (every wave streams the same region at once)
-  const int nch = D / kLg2Chunk;
-  const size_t chunk_halves = (size_t)emb_groups16(V) * KS * NS * 512;
-  const _Float16* er = emb2 + (size_t)(v0 / 16) * KS * NS * 512 + lane * 8;
-  floatx4 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) acc[a][b] = floatx4{0.f, 0.f, 0.f, 0.f};
-  half8 ec[2][KS][NS], en[2][KS][NS];
-  auto load_e = [&](half8 (&e)[2][KS][NS], int kc) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int p = 0; p < NS; ++p)  // D % kLg2Chunk == 0 (launcher): always in range
-          e[mt][ks][p] = WA_LOGITS_NT ? __builtin_nontemporal_load(reinterpret_cast<const half8*>(
-                                            er + (kc / kLg2Chunk) * chunk_halves + ((mt * KS + ks) * NS + p) * 512))
-                                      : *reinterpret_cast<const half8*>(er + (kc / kLg2Chunk) * chunk_halves +
-                                                                         ((mt * KS + ks) * NS + p) * 512);
-  };
-  // the hidden fragments of chunk c: A-tiled m-tile 0, blocks 4c .. 4c + 3
-  // (kk, plane, lane: 1 KiB each, contiguous), staged through registers into
-  // LDS buffer c & 1 lane-linear.  Not global_load_lds: while an LDS DMA is in
-  // flight hipcc waits vmcnt(0) at the first use of any ordinary load result
-  // (cdna_hip_programming.md "Pipelining across barriers"), which would drain
-  // the next chunk's table loads at the first MFMA of every chunk.
-  constexpr int HPT = HCH / (256 * 16);  // 16-B pieces per thread per chunk
-  half8 hr[HPT];
-  auto load_h = [&](int c) {
-    const uint8_t* src = reinterpret_cast<const uint8_t*>(htiled) + (size_t)c * HCH;
-#pragma unroll
-    for (int i = 0; i < HPT; ++i) hr[i] = *reinterpret_cast<const half8*>(src + (i * 256 + tid) * 16);
-  };
-  auto store_h = [&](int c) {
-#pragma unroll
-    for (int i = 0; i < HPT; ++i) *reinterpret_cast<half8*>(smem + (c & 1) * HCH + (i * 256 + tid) * 16) = hr[i];
-  };
-  load_h(0);
-  load_e(ec, 0);
-  store_h(0);
-  __syncthreads();
-  for (int c = 0; c < nch; ++c) {
-    // hidden c + 1 first (its wait after the MFMAs then leaves the table loads
-    // in flight), the next chunk's table second
-    if (c + 1 < nch) load_h(c + 1);
-    load_e(en, c + 1 < nch ? (c + 1) * kLg2Chunk : c * kLg2Chunk);  // the last chunk re-loads itself
-    // keep the loads here: left to itself the scheduler sinks them below the
-    // MFMAs (fewer live registers), and every chunk then waits a full latency
-    __builtin_amdgcn_sched_barrier(0);
-    const uint8_t* hb = smem + (c & 1) * HCH;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        // B: clip 16 nt + l16, dims 32 ks + 8 lq .. + 7 = fragment (ks, kk = lq >> 1),
-        // lane' = clip + 32 (lq & 1)
-        const int off = ((ks * 2 + (lq >> 1)) * NS) * 1024 + (16 * nt + l16 + 32 * (lq & 1)) * 16;
-        const half8 bh = *reinterpret_cast<const half8*>(hb + off);
-        half8 bl;
-        if constexpr (NS == 2) bl = *reinterpret_cast<const half8*>(hb + off + 1024);
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ec[mt][ks][0], bh, acc[mt][nt], 0, 0, 0);
-          if constexpr (NS == 2) {
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ec[mt][ks][1], bh, acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ec[mt][ks][0], bl, acc[mt][nt], 0, 0, 0);
-          }
-        }
-      }
-    }
-    // buffer (c + 1) & 1 was last read in chunk c - 1, before the previous barrier
-    if (c + 1 < nch) store_h(c + 1);
-    __syncthreads();  // no LDS DMA in flight: a bare s_barrier, the table loads survive it
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int p = 0; p < NS; ++p) ec[mt][ks][p] = en[mt][ks][p];
-  }
-  // acc[mt][nt]: lane holds clip 16 nt + l16, vocab v0 + 16 mt + 4 lq + j
-  const int suppress = state->step + 1 < min_tokens;
-  bool bad = false;
-  int4 rule[2] = {};  // TS: the records of this lane's two clips (a padded clip reads the last one's)
-  if constexpr (TS) {
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-      rule[nt] = *reinterpret_cast<const int4*>(ts.rules + min(16 * nt + l16, B - 1));
-  }
-#pragma unroll
-  for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int vl = 16 * mt + 4 * lq + j;
-        const int n = v0 + vl;
-        float v = acc[mt][nt][j] * kLgInv;
-        bad |= n < V && 16 * nt + l16 < B && !__builtin_isfinite(v);
-        if constexpr (TS) {
-          if (n >= V || ts_masked(n, ts.ts0, rule[nt], suppress != 0)) v = -INFINITY;
-        } else {
-          if (n >= V || (suppress && n == kEOT)) v = -INFINITY;
-        }
-        lg[(16 * nt + l16) * kLgPickLd + wave * 32 + vl] = v;
-      }
-  // an MFMA operand out of the f16-pair range upstream turns every logit of
-  // the clip into inf / NaN: flag it (plain vector store, every writer stores 1)
-  if (bad && range_flag) *range_flag = 1;
-  if (trace_out) {  // diagnostics only: uniform branch
-    __syncthreads();
-    const int slot = state->step + 1;
-    if (slot < trace_s1)
-      for (int e = tid; e < B * trace_k; e += 256) {
-        const int b = e / trace_k;
-        const size_t o = ((size_t)b * trace_s1 + slot) * trace_k + (e - b * trace_k);
-        const int id = trace_ids[o] - (int)blockIdx.x * 128;
-        if (id >= 0 && id < 128) trace_out[o] = lg[b * kLgPickLd + id];
-      }
-  }
-  if constexpr (SAMPLE)
-    pick_from_lds_sample<TS>(lg, B, V, state->step + 1, ts, counter, out_tok, out_lp, ticket);
-  else if constexpr (TS)
-    pick_from_lds_ts(lg, B, V, ts, pval, pidx, psum, counter, out_tok, out_lp, ticket);
-  else
-    pick_from_lds<SCORE>(lg, B, V, pval, pidx, psum, counter, out_tok, out_lp, ticket);
-}
-
-int logits_argmax_groups(int V) { return (V + 127) / 128; }
-
-// f32 rows -> fragment-tiled f16 planes, chunk-major: fragment
-// f = (chunk * groups + g) * KS + ks holds rows 16 g .. + 15, dims
-// 128 chunk + 32 ks + 8 (lane >> 4) .. + 7; thread = (fragment, lane): 8 values
-template <int NS>
-__global__ __launch_bounds__(256) void emb_tiled_kernel(const float* __restrict__ x, int V, int D, int64_t nfrag,
-                                                        _Float16* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= nfrag * 64) return;
-  const int lane = (int)(i & 63);
-  constexpr int KS = kLg2Chunk / 32;
-  const int64_t f = i >> 6;
-  const int64_t groups = emb_groups16(V);
-  const int64_t cg = f / KS;  // chunk * groups + g
-  const int64_t chunk = cg / groups, g = cg - chunk * groups;
-  const int s = (int)(chunk * KS + (f - cg * KS));
-  const int64_t v = g * 16 + (lane & 15);
-  const int k = s * 32 + 8 * (lane >> 4);
-  half8 hi, lo;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    _Float16 a = (_Float16)0.0f, b = (_Float16)0.0f;
-    if (v < V) split_f16(x[v * D + k + j] * kEmbScale, a, b);
-    hi[j] = a;
-    lo[j] = b;
-  }
-  *reinterpret_cast<half8*>(out + (f * NS + 0) * 512 + lane * 8) = hi;
-  if constexpr (NS == 2) *reinterpret_cast<half8*>(out + (f * NS + 1) * 512 + lane * 8) = lo;
-}
-
-bool emb_tiled_supported(int D) { return D % kLg2Chunk == 0; }
-int64_t emb_tiled_rows(int V) { return (int64_t)logits_argmax_groups(V) * 128; }
-
-hipError_t launch_emb_tiled(const float* emb, int V, int D, int ns, _Float16* out, hipStream_t st) {
-  if (!emb_tiled_supported(D) || (ns != 1 && ns != 2)) return hipErrorInvalidValue;
-  const int64_t nfrag = emb_tiled_rows(V) / 16 * (D / 32);
-  const dim3 g((unsigned)((nfrag * 64 + 255) / 256));
-  if (ns == 2)
-    hipLaunchKernelGGL(emb_tiled_kernel<2>, g, dim3(256), 0, st, emb, V, D, nfrag, out);
-  else
-    hipLaunchKernelGGL(emb_tiled_kernel<1>, g, dim3(256), 0, st, emb, V, D, nfrag, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_logits_argmax(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
-                                int min_tokens, const DecodeState* state, float* pval, int* pidx, int* counter,
-                                int* out_tok, const int* trace_ids, float* trace_out, int trace_s1, int trace_k,
-                                int* range_flag, hipStream_t st) {
-  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled) return hipErrorInvalidValue;
-  const dim3 grid(logits_argmax_groups(V));
-  float* const none = nullptr;
-  if (ns == 2)
-    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 0>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
-                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, none, none, TsArgs{});
-  else
-    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 0>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
-                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, none, none, TsArgs{});
-  return hipGetLastError();
-}
-
-hipError_t launch_logits_argmax_scored(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
-                                       int min_tokens, const DecodeState* state, float* pval, int* pidx, float* psum,
-                                       int* counter, int* out_tok, float* out_lp, const int* trace_ids,
-                                       float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st) {
-  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled || !psum || !out_lp)
-    return hipErrorInvalidValue;
-  const dim3 grid(logits_argmax_groups(V));
-  if (ns == 2)
-    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
-                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, psum, out_lp, TsArgs{});
-  else
-    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
-                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, psum, out_lp, TsArgs{});
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------ row log-prob --
-// out[row * out_stride] = z[id] - logsumexp(z[lo:hi]) of the stored logit row
-// z = logits + row * ld, id = idx ? idx[row * idx_stride] : fixed_idx, EOT
-// treated as -inf when mask_eot (the pick's own masking, whisper.rs:97-98,
-// 120-122; mask_state: when mask_state->step + 1 < min_tokens instead).  One
-// workgroup per row, two passes over the range: the maximum, then
-// sum exp(z - max) -- per thread ceil((hi - lo) / 256) terms, 6 shuffle adds,
-// 3 adds over the waves -- and z[id] - max - log(sum).  A -inf entry adds 0;
-// an id outside [lo, hi) or a row with no finite entry gives NaN.
-__global__ __launch_bounds__(256) void row_logprob_kernel(const float* __restrict__ logits, int64_t ld, int lo, int hi,
-                                                          int mask_eot, int min_tokens,
-                                                          const DecodeState* __restrict__ mask_state,
-                                                          const int* __restrict__ idx, int idx_stride, int fixed_idx,
-                                                          float* __restrict__ out, int out_stride) {
-  __shared__ float sm[4];
-  __shared__ float ss[4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* z = logits + (size_t)b * ld;
-  const bool mask = mask_state ? (mask_state->step + 1 < min_tokens) : mask_eot != 0;
-  float m = -INFINITY;
-  for (int i = lo + tid; i < hi; i += 256) {
-    const float v = (mask && i == kEOT) ? -INFINITY : z[i];
-    m = fmaxf(m, v);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if (lane == 0) sm[wave] = m;
-  __syncthreads();
-  m = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-  float s = 0.0f;
-  if (m > -INFINITY)
-    for (int i = lo + tid; i < hi; i += 256) {
-      const float v = (mask && i == kEOT) ? -INFINITY : z[i];
-      s += expf(v - m);
-    }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) ss[wave] = s;
-  __syncthreads();
-  if (tid == 0) {
-    s = ((ss[0] + ss[1]) + ss[2]) + ss[3];
-    const int id = idx ? idx[(size_t)b * idx_stride] : fixed_idx;
-    float r = NAN;
-    if (id >= lo && id < hi && m > -INFINITY) {
-      const float v = (mask && id == kEOT) ? -INFINITY : z[id];
-      r = (v - m) - logf(s);
-    }
-    out[(size_t)b * out_stride] = r;
-  }
-}
-
-hipError_t launch_row_logprob(const float* logits, int rows, int64_t ld, int lo, int hi, int mask_eot, int min_tokens,
-                              const DecodeState* mask_state, const int* idx, int idx_stride, int fixed_idx, float* out,
-                              int out_stride, hipStream_t st) {
-  if (rows < 1 || lo < 0 || lo >= hi || hi > ld || !logits || !out) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(row_logprob_kernel, dim3(rows), dim3(256), 0, st, logits, ld, lo, hi, mask_eot, min_tokens,
-                     mask_state, idx, idx_stride, fixed_idx, out, out_stride);
-  return hipGetLastError();
-}
-
-// exp of every entry, in place (row log-probabilities -> probabilities)
-__global__ void exp_inplace_kernel(float* __restrict__ x, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) x[i] = expf(x[i]);
-}
-
-hipError_t launch_exp_inplace(float* x, int n, hipStream_t st) {
-  hipLaunchKernelGGL(exp_inplace_kernel, dim3((n + 255) / 256), dim3(256), 0, st, x, n);
-  return hipGetLastError();
-}
-
-// ------------------------------------------------------------ bookkeep --
-__global__ void bookkeep_kernel(const int* __restrict__ next, int* __restrict__ tokens, int* __restrict__ ntok,
-                                int* __restrict__ done, int B, int max_tokens, int eot_stop, DecodeState* state) {
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    if (!done[b]) {
-      const int tk = next[b];
-      if (eot_stop && tk == kEOT) {
-        done[b] = 1;
-        atomicAdd(&state->n_done, 1);
-      } else if (ntok[b] < max_tokens) {
-        tokens[(size_t)b * max_tokens + ntok[b]] = tk;
-        ntok[b] += 1;
-      }
-    }
-  }
-  if (threadIdx.x == 0) {
-    state->position += 1;
-    state->kv_len += 1;
-    state->step += 1;
-  }
-}
-
-hipError_t launch_bookkeep(const int* next_tok, int* tokens, int* n_tokens, int* done, int B, int max_tokens,
-                           int eot_stop, DecodeState* state, hipStream_t st) {
-  hipLaunchKernelGGL(bookkeep_kernel, dim3(1), dim3(256), 0, st, next_tok, tokens, n_tokens, done, B, max_tokens,
-                     eot_stop, state);
-  return hipGetLastError();
-}
-
-// bookkeep_kernel of a scored transcribe: the pick's log-probability next_lp[b]
-// goes where its token goes, logprob[b][ntok[b]] (rows of max_tokens + 1), and
-// the EOT pick that ends a clip leaves its own in the slot after the clip's
-// last token.
-__global__ void bookkeep_scored_kernel(const int* __restrict__ next, const float* __restrict__ next_lp,
-                                       int* __restrict__ tokens, float* __restrict__ logprob, int* __restrict__ ntok,
-                                       int* __restrict__ done, int B, int max_tokens, int eot_stop,
-                                       DecodeState* state) {
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    if (!done[b]) {
-      const int tk = next[b];
-      const float lp = next_lp[b];
-      if (eot_stop && tk == kEOT) {
-        done[b] = 1;
-        atomicAdd(&state->n_done, 1);
-        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
-      } else if (ntok[b] < max_tokens) {
-        tokens[(size_t)b * max_tokens + ntok[b]] = tk;
-        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
-        ntok[b] += 1;
-      }
-    }
-  }
-  if (threadIdx.x == 0) {
-    state->position += 1;
-    state->kv_len += 1;
-    state->step += 1;
-  }
-}
-
-hipError_t launch_bookkeep_scored(const int* next_tok, const float* next_lp, int* tokens, float* logprob,
-                                  int* n_tokens, int* done, int B, int max_tokens, int eot_stop, DecodeState* state,
-                                  hipStream_t st) {
-  hipLaunchKernelGGL(bookkeep_scored_kernel, dim3(1), dim3(256), 0, st, next_tok, next_lp, tokens, logprob, n_tokens,
-                     done, B, max_tokens, eot_stop, state);
-  return hipGetLastError();
-}
-
-// dst[i] = src[i * stride], i < n
-__global__ void gather_int_kernel(const int* __restrict__ src, int stride, int* __restrict__ dst, int n) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dst[i] = src[(size_t)i * stride];
-}
-
-hipError_t launch_gather_int(const int* src, int stride, int* dst, int n, hipStream_t st) {
-  hipLaunchKernelGGL(gather_int_kernel, dim3((n + 255) / 256), dim3(256), 0, st, src, stride, dst, n);
-  return hipGetLastError();
-}
-
-// ----------------------------------------- timestamp decoding, launches --
-// Kept behind every other kernel of this file: the fused kernel's TS
-// instantiations, the row kernel and the bookkeeping kernel are emitted after
-// the kernels that were here before them, which keep their places in the code
-// object.
-hipError_t launch_logits_argmax_ts(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
-                                   int min_tokens, const DecodeState* state, const TsRule* rules, int ts0,
-                                   float* pval, int* pidx, float* psum, float* xval, int* xidx, float* xsum,
-                                   int* counter, int* out_tok, float* out_lp, int* out_mass, const int* trace_ids,
-                                   float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st) {
-  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled || !psum || !out_lp || !rules ||
-      !xval || !xidx || !xsum || ts0 < 1)
-    return hipErrorInvalidValue;
-  const dim3 grid(logits_argmax_groups(V));
-  const TsArgs ts{rules, ts0, xval, xidx, xsum, out_mass};
-  if (ns == 2)
-    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<2, 1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
-                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, psum, out_lp, ts);
-  else
-    hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<1, 1, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V,
-                       min_tokens, state, pval, pidx, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,
-                       range_flag, psum, out_lp, ts);
-  return hipGetLastError();
-}
-
-// -------------------------------------------- timestamp pick of a row --
-// The timestamp rule over a stored logit row (the prompt's pick, decode
-// groups wider than 32 rows): one workgroup per row, two passes -- each
-// side's (max, index) under ts_masked, then each side's sum exp(z - max) --
-// and ts_decide in thread 0.  Per side a thread adds ceil(V / 256) terms, 6
-// shuffle adds, 3 adds over the waves.
-__global__ __launch_bounds__(256) void row_timestamp_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                            int suppress_fixed, int min_tokens,
-                                                            const DecodeState* __restrict__ state,
-                                                            const TsRule* __restrict__ rules, int ts0,
-                                                            int* __restrict__ out_tok, float* __restrict__ out_lp,
-                                                            int* __restrict__ out_mass, int* __restrict__ range_flag) {
-  __shared__ float sv[2][4], ss[2][4];
-  __shared__ int si[2][4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* z = logits + (size_t)b * ld;
-  const bool suppress = state ? (state->step + 1 < min_tokens) : suppress_fixed != 0;
-  const int4 rule = *reinterpret_cast<const int4*>(rules + b);
-  float tv = -INFINITY, xv = -INFINITY;
-  int ti = -1, xi = -1;
-  bool bad = false;
-  for (int i = tid; i < V; i += 256) {
-    float v = z[i];
-    bad |= !__builtin_isfinite(v);
-    if (ts_masked(i, ts0, rule, suppress)) v = -INFINITY;
-    if (i < ts0)
-      better(tv, ti, v, i);
-    else
-      better(xv, xi, v, i);
-  }
-  if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v2 = __shfl_xor(tv, o, 64), v3 = __shfl_xor(xv, o, 64);
-    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
-    better(tv, ti, v2, i2);
-    better(xv, xi, v3, i3);
-  }
-  if (lane == 0) {
-    sv[0][wave] = tv;
-    si[0][wave] = ti;
-    sv[1][wave] = xv;
-    si[1][wave] = xi;
-  }
-  __syncthreads();
-  tv = xv = -INFINITY;
-  ti = xi = -1;
-  for (int w = 0; w < 4; ++w) {
-    better(tv, ti, sv[0][w], si[0][w]);
-    better(xv, xi, sv[1][w], si[1][w]);
-  }
-  float s_t = 0.0f, s_x = 0.0f;
-  for (int i = tid; i < V; i += 256) {
-    const float v = ts_masked(i, ts0, rule, suppress) ? -INFINITY : z[i];
-    if (i < ts0) {
-      if (tv > -INFINITY) s_t += expf(v - tv);
-    } else {
-      if (xv > -INFINITY) s_x += expf(v - xv);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s_t += __shfl_xor(s_t, o, 64);
-    s_x += __shfl_xor(s_x, o, 64);
-  }
-  if (lane == 0) {
-    ss[0][wave] = s_t;
-    ss[1][wave] = s_x;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    s_t = ((ss[0][0] + ss[0][1]) + ss[0][2]) + ss[0][3];
-    s_x = ((ss[1][0] + ss[1][1]) + ss[1][2]) + ss[1][3];
-    int tok, mass;
-    float lp;
-    ts_decide(tv, ti, s_t, xv, xi, s_x, tok, lp, mass);
-    out_tok[b] = tok;
-    if (out_lp) out_lp[b] = lp;
-    if (out_mass) out_mass[b] = mass;
-  }
-}
-
-hipError_t launch_row_timestamp(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
-                                const DecodeState* state, const TsRule* rules, int ts0, int* out_tok, float* out_lp,
-                                int* out_mass, int* range_flag, hipStream_t st) {
-  if (rows < 1 || V < 1 || V > ld || !logits || !rules || !out_tok || ts0 < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(row_timestamp_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, suppress_eot, min_tokens,
-                     state, rules, ts0, out_tok, out_lp, out_mass, range_flag);
-  return hipGetLastError();
-}
-
-// bookkeep_scored_kernel of a timestamp transcribe: every row's rule record
-// also advances by the token that is fed to this step (ts_rule_step), done
-// clips included -- their picks go nowhere, and a record of any history leaves
-// a non-empty allowed set.
-__global__ void bookkeep_ts_kernel(const int* __restrict__ next, const float* __restrict__ next_lp,
-                                   int* __restrict__ tokens, float* __restrict__ logprob, int* __restrict__ ntok,
-                                   int* __restrict__ done, int B, int max_tokens, int eot_stop, DecodeState* state,
-                                   TsRule* __restrict__ rules, int ts0, int V) {
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const int tk = next[b];
-    if (!done[b]) {
-      const float lp = next_lp[b];
-      if (eot_stop && tk == kEOT) {
-        done[b] = 1;
-        atomicAdd(&state->n_done, 1);
-        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
-      } else if (ntok[b] < max_tokens) {
-        tokens[(size_t)b * max_tokens + ntok[b]] = tk;
-        logprob[(size_t)b * (max_tokens + 1) + ntok[b]] = lp;
-        ntok[b] += 1;
-      }
-    }
-    rules[b] = ts_rule_step(rules[b], tk, ts0, V);
-  }
-  if (threadIdx.x == 0) {
-    state->position += 1;
-    state->kv_len += 1;
-    state->step += 1;
-  }
-}
-
-hipError_t launch_bookkeep_ts(const int* next_tok, const float* next_lp, int* tokens, float* logprob, int* n_tokens,
-                              int* done, int B, int max_tokens, int eot_stop, DecodeState* state, TsRule* rules,
-                              int ts0, int V, hipStream_t st) {
-  hipLaunchKernelGGL(bookkeep_ts_kernel, dim3(1), dim3(256), 0, st, next_tok, next_lp, tokens, logprob, n_tokens, done,
-                     B, max_tokens, eot_stop, state, rules, ts0, V);
-  return hipGetLastError();
-}
-
-// ------------------------------------ temperature sampling, launches --
-// Behind the timestamp kernels, for the same reason they are behind the rest.
-int64_t logits_sample_scratch_floats(int V) { return (int64_t)2 * kSmpArrays * 32 * logits_argmax_groups(V); }
-
-hipError_t launch_logits_argmax_sample(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
-                                       int min_tokens, const DecodeState* state, const float* temp,
-                                       const uint64_t* seed, const TsRule* rules, int ts0, float* scr, int* counter,
-                                       int* out_tok, float* out_lp, int* out_mass, const int* trace_ids,
-                                       float* trace_out, int trace_s1, int trace_k, int* range_flag, hipStream_t st) {
-  if (B < 1 || B > 32 || !emb_tiled_supported(D) || !state || !emb2 || !htiled || !out_lp || !temp || !seed || !scr ||
-      (rules && ts0 < 1))
-    return hipErrorInvalidValue;
-  const dim3 grid(logits_argmax_groups(V));
-  SampleArgs a{};
-  a.rules = rules;
-  a.ts0 = ts0;
-  a.out_mass = out_mass;
-  a.temp = temp;
-  a.seed = seed;
-  a.scr = scr;
-  float* const nf = nullptr;
-  int* const ni = nullptr;
-#define WA_SAMPLE_LAUNCH(NS_, TS_)                                                                                  \
-  hipLaunchKernelGGL((logits_argmax_f16_k32_kernel<NS_, 1, TS_, 1>), grid, dim3(256), 0, st, htiled, B, D, emb2, V, \
-                     min_tokens, state, nf, ni, counter, out_tok, trace_ids, trace_out, trace_s1, trace_k,           \
-                     range_flag, nf, out_lp, a)
-  if (rules) {
-    if (ns == 2)
-      WA_SAMPLE_LAUNCH(2, 1);
-    else
-      WA_SAMPLE_LAUNCH(1, 1);
-  } else {
-    if (ns == 2)
-      WA_SAMPLE_LAUNCH(2, 0);
-    else
-      WA_SAMPLE_LAUNCH(1, 0);
-  }
-#undef WA_SAMPLE_LAUNCH
-  return hipGetLastError();
-}
-
-// ---------------------------------------------- sampled pick of a row --
-// The sampled pick over a stored logit row (the prompt's pick, pick 0, and
-// decode groups wider than 32 rows), plain (rules null: EOT suppression only,
-// the whole row one side) or under the timestamp rule: row_logprob_kernel's /
-// row_timestamp_kernel's two passes and order of additions, with each side's
-// best key carried beside its raw maximum; thread 0 decides as
-// pick_from_lds_sample does.
-__global__ __launch_bounds__(256) void row_sample_kernel(const float* __restrict__ logits, int64_t ld, int V,
-                                                         int suppress_fixed, int min_tokens,
-                                                         const DecodeState* __restrict__ state,
-                                                         const TsRule* __restrict__ rules, int ts0_rule,
-                                                         const float* __restrict__ temp,
-                                                         const uint64_t* __restrict__ seed, int pick_fixed,
-                                                         int* __restrict__ out_tok, float* __restrict__ out_lp,
-                                                         int* __restrict__ out_mass, int* __restrict__ range_flag) {
-  __shared__ float sm[2][4], sk[2][4], sz[2][4], ss[2][4];
-  __shared__ int si[2][4];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* z = logits + (size_t)b * ld;
-  const bool suppress = state ? (state->step + 1 < min_tokens) : suppress_fixed != 0;
-  const int pick = state ? state->step + 1 : pick_fixed;
-  const int ts0 = rules ? ts0_rule : V;
-  int4 rule = {};
-  if (rules) rule = *reinterpret_cast<const int4*>(rules + b);
-  auto masked = [&](int i) { return rules ? ts_masked(i, ts0, rule, suppress) : (suppress && i == kEOT); };
-  const float T = temp[b];
-  const uint64_t k = T > 0.0f ? smp_pick_key(seed[b], pick) : 0;
-  float tm = -INFINITY, xm = -INFINITY, tk = -INFINITY, xk = -INFINITY, tz = -INFINITY, xz = -INFINITY;
-  int ti = -1, xi = -1;
-  bool bad = false;
-  for (int i = tid; i < V; i += 256) {
-    float v = z[i];
-    bad |= !__builtin_isfinite(v);
-    if (masked(i)) v = -INFINITY;
-    const float key = smp_key(v, T, k, i);
-    if (i < ts0) {
-      tm = fmaxf(tm, v);
-      better_key(tk, ti, tz, key, i, v);
-    } else {
-      xm = fmaxf(xm, v);
-      better_key(xk, xi, xz, key, i, v);
-    }
-  }
-  if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    tm = fmaxf(tm, __shfl_xor(tm, o, 64));
-    xm = fmaxf(xm, __shfl_xor(xm, o, 64));
-    const float k2 = __shfl_xor(tk, o, 64), z2 = __shfl_xor(tz, o, 64);
-    const float k3 = __shfl_xor(xk, o, 64), z3 = __shfl_xor(xz, o, 64);
-    const int i2 = __shfl_xor(ti, o, 64), i3 = __shfl_xor(xi, o, 64);
-    better_key(tk, ti, tz, k2, i2, z2);
-    better_key(xk, xi, xz, k3, i3, z3);
-  }
-  if (lane == 0) {
-    sm[0][wave] = tm;
-    sk[0][wave] = tk;
-    sz[0][wave] = tz;
-    si[0][wave] = ti;
-    sm[1][wave] = xm;
-    sk[1][wave] = xk;
-    sz[1][wave] = xz;
-    si[1][wave] = xi;
-  }
-  __syncthreads();
-  tm = xm = tk = xk = tz = xz = -INFINITY;
-  ti = xi = -1;
-  for (int w = 0; w < 4; ++w) {
-    tm = fmaxf(tm, sm[0][w]);
-    xm = fmaxf(xm, sm[1][w]);
-    better_key(tk, ti, tz, sk[0][w], si[0][w], sz[0][w]);
-    better_key(xk, xi, xz, sk[1][w], si[1][w], sz[1][w]);
-  }
-  float s_t = 0.0f, s_x = 0.0f;
-  for (int i = tid; i < V; i += 256) {
-    const float v = masked(i) ? -INFINITY : z[i];
-    if (i < ts0) {
-      if (tm > -INFINITY) s_t += expf(v - tm);
-    } else {
-      if (xm > -INFINITY) s_x += expf(v - xm);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s_t += __shfl_xor(s_t, o, 64);
-    s_x += __shfl_xor(s_x, o, 64);
-  }
-  if (lane == 0) {
-    ss[0][wave] = s_t;
-    ss[1][wave] = s_x;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    s_t = ((ss[0][0] + ss[0][1]) + ss[0][2]) + ss[0][3];
-    s_x = ((ss[1][0] + ss[1][1]) + ss[1][2]) + ss[1][3];
-    int unused, mass;
-    float lpg;
-    ts_decide(tm, 0, s_t, xm, 0, s_x, unused, lpg, mass);  // an empty timestamp side: -log s_t, no mass
-    int tok = ti;
-    float Ms = fmaxf(tm, xm), zt = tz;
-    if (mass) {
-      Ms = xm;
-      tok = xi;
-      zt = xz;
-    } else {
-      better_key(tk, tok, zt, xk, xi, xz);
-    }
-    const float d = zt - Ms;
-    out_tok[b] = tok < 0 ? 0 : tok;
-    if (out_lp) out_lp[b] = d == 0.0f ? lpg : d + lpg;
-    if (out_mass) out_mass[b] = mass;
-  }
-}
-
-hipError_t launch_row_sample(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
-                             const DecodeState* state, const TsRule* rules, int ts0, const float* temp,
-                             const uint64_t* seed, int pick, int* out_tok, float* out_lp, int* out_mass,
-                             int* range_flag, hipStream_t st) {
-  if (rows < 1 || V < 1 || V > ld || !logits || !out_tok || !temp || !seed || (rules && ts0 < 1) || pick < 0)
-    return hipErrorInvalidValue;
-  hipLaunchKernelGGL(row_sample_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, suppress_eot, min_tokens, state,
-                     rules, ts0, temp, seed, pick, out_tok, out_lp, out_mass, range_flag);
   return hipGetLastError();
 }
 

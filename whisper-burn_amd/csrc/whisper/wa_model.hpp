@@ -14,6 +14,7 @@
 #include "../../../include/wq4.h"
 #include "wa_gguf.hpp"
 #include "wa_kernels.hpp"
+#include "wa_pick.hpp"
 
 namespace wa {
 
@@ -140,32 +141,26 @@ struct DecGroup {
   int* xkv_ctr;       //   and the per-(clip, head) arrival counters
   _Float16* atd_ln;   // LayerNorm fold: A-tiled x * gamma of the next LayerNorm
   float* ln_stats;    //                 its per (row, 32-column tile) mean / M2
-  _Float16* hid_t;    // fused logits + argmax: the final LN, A-tiled (m-tile 0)
-  float* lg_val;      //                        per-workgroup candidates [32][groups]
-  int *lg_idx, *lg_ctr;
+  _Float16* hid_t;    // fused logits + pick: the final LN, A-tiled (m-tile 0)
+  float* lg_scr;      //                      the workgroups' candidates (PickArgs::scratch)
+  int* lg_ctr;
   // scored transcribes (wa_transcribe_scored; allocated by the first one,
   // ensure_score_buffers): the log-probability of next_tok, every stored
-  // pick's [nb][kMaxTokens + 1] (NaN where nothing was stored), the fused
-  // kernel's per-workgroup sums [32][groups], the prompt's no-speech and
-  // language probabilities with the language token, and the SOT position's
-  // logit rows [nb][n_vocab] of an explicit-language prompt
-  float *next_lp = nullptr, *logprob = nullptr, *lg_sum = nullptr;
+  // pick's [nb][kMaxTokens + 1] (NaN where nothing was stored), the prompt's
+  // no-speech and language probabilities with the language token, and the SOT
+  // position's logit rows [nb][n_vocab] of an explicit-language prompt
+  float *next_lp = nullptr, *logprob = nullptr;
   float *no_speech = nullptr, *lang_prob = nullptr, *z0 = nullptr;
   int* lang_tok = nullptr;
   // timestamp transcribes (wa_transcribe_timestamps; allocated by the first
   // one, ensure_ts_buffers): every clip's rule record, advanced by the
-  // bookkeeping kernel, and the fused kernel's timestamp-side candidates,
-  // indices and sums [32][groups] beside lg_val / lg_idx / lg_sum
+  // bookkeeping kernel
   TsRule* ts_rules = nullptr;
-  float *lg_xval = nullptr, *lg_xsum = nullptr;
-  int* lg_xidx = nullptr;
   // sampled transcribes (wa_transcribe_sampled; allocated by the first one,
   // ensure_sample_buffers): the clips' temperatures and seeds, uploaded by
-  // every prompt from the caller's arrays at clip `clip0` of them, and the
-  // sampled fused kernel's scratch block (launch_logits_argmax_sample)
+  // every prompt from the caller's arrays at clip `clip0` of them
   float* smp_temp = nullptr;
   uint64_t* smp_seed = nullptr;
-  float* smp_scr = nullptr;
   int clip0 = 0;  // this group's first clip in the call's per-clip host arrays (run_decode)
   DecodeState* state;
   void* ffn_ws = nullptr;  // range tier 2: wq4_ffn_forward_ws workspace (4 * nb rows)
