@@ -47,4 +47,39 @@ void mel_pack_consts(const MelBank& bank, uint8_t* host);
 hipError_t launch_log_mel(const float* audio, int B, int64_t n_samples, int64_t ld_audio, int n_mels,
                           const uint8_t* consts, float* part, float* out, hipStream_t st);
 
+// ---- windows of long recordings (wa_long_mel_max / wa_long_mel_windows) ----
+// OpenAI audio.py / transcribe.py semantics, not the reference's (which
+// truncates to 30 s, transcribe.rs:49-51): the recording is zero-extended,
+// reflected about sample 0 on the left only, raw frame f covers samples
+// 160 f - 200 .. 160 f + 199, and a window is normalised against the maximum
+// of its whole recording (include/whisper_amd.h has the definitions).  No
+// recording-length mel is stored: mel_stream_max keeps only maxima, and
+// mel_window computes the 3000 frames of a window again, already normalised.
+
+// One recording of the flat workgroup list of launch_long_mel_max.
+struct MelStream {
+  int64_t offset;    // first sample, from the launch's audio pointer
+  int64_t n;         // samples
+  int64_t frames;    // raw frames that can exceed -10: ceil((n + 200) / 160)
+  int64_t wg_first;  // prefix sum of ceil(frames / 8) over the recordings before
+};
+// One window of launch_long_mel_windows (the device descriptor of a clip).
+struct MelWindow {
+  int64_t offset, n;  // the recording, as above
+  int32_t seek;       // first raw frame of the window, 0 <= seek < n / 160
+  int32_t max_index;  // the recording's entry of max_dev
+};
+
+// recordings are shorter than this: seek + 3000 frames stays an int32
+constexpr int64_t kMelLongMaxSamples = (int64_t)kMelHop * (2147483647LL - kMelFrames - 1);
+inline int64_t mel_stream_frames(int64_t n) { return (n + kMelNfft / 2 + kMelHop - 1) / kMelHop; }
+
+// max_out[r] = max(-10, max of recording r's raw frames); part: n_wg floats
+// of scratch, n_wg the table's total workgroup count (< 2^31).
+hipError_t launch_long_mel_max(const float* audio, const MelStream* streams, int n_streams, int64_t n_wg, int n_mels,
+                               const uint8_t* consts, float* part, float* max_out, hipStream_t st);
+// out: [B][n_mels][3000], window b from wins[b] (device), zeros past its size.
+hipError_t launch_long_mel_windows(const float* audio, const MelWindow* wins, int B, const float* max_dev, int n_mels,
+                                   const uint8_t* consts, float* out, hipStream_t st);
+
 }  // namespace wa

@@ -1,6 +1,6 @@
 // wa_model.hpp -- internal: the Whisper model runtime's state (struct
 // wa_model) and what its translation units (wa_weights, wa_forward,
-// wa_transcribe, wa_api, wa_checks .cpp) need from one another.
+// wa_transcribe, wa_long, wa_api, wa_checks .cpp) need from one another.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -371,5 +371,12 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
                            int kv0, hipStream_t st);
 wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st);
 wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop);
+
+// ---- wa_transcribe.cpp
+bool bad_temperatures(const float* t, int n);  // one is negative or not finite
+// The ladder of wa_transcribe_fallback on checked arguments (wa_long.cpp runs it per round).
+wq4_status transcribe_ladder(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                             int eot_stop, const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
+                             const wa_scores* scores, int32_t* rung_out, void* stream);
 
 }  // namespace wa

@@ -606,7 +606,7 @@ static wq4_status with_sampling(wa_model* m, const float* temp, const uint64_t* 
   return s;
 }
 
-static bool bad_temperatures(const float* t, int n) {
+bool wa::bad_temperatures(const float* t, int n) {
   for (int i = 0; i < n; ++i)
     if (!(t[i] >= 0.0f) || !std::isfinite(t[i])) return true;
   return false;
@@ -621,6 +621,73 @@ static wq4_status raise_tier(wa_model* m) {
   if (m->range_tier == 1) WA_TRY(ensure_ffn_ws(m));  // entering tier 2
   ++m->range_tier;
   return WQ4_OK;
+}
+
+// The temperature ladder of wa_transcribe_fallback (and of every round of
+// wa_transcribe_long), its arguments checked by the entry: one encoder pass,
+// then per rung a prompt + decode over the same planes with the clips that
+// have passed frozen.
+wq4_status wa::transcribe_ladder(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                 int eot_stop, const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
+                                 const wa_scores* scores, int32_t* rung_out, void* stream) {
+  const int B = n_clips, R = fb->n_temperatures;
+  const size_t slots = (size_t)max_tokens + 1;
+  std::vector<float> temp(B);
+  std::vector<uint64_t> seed(B);
+  return with_sampling(m, temp.data(), seed.data(), fb->timestamps, fb->max_initial, [&]() -> wq4_status {
+    // one rung's results; the clips it was run for are copied to the caller's arrays
+    std::vector<int32_t> tok((size_t)B * max_tokens), nt(B), lt(B);
+    std::vector<float> lp((size_t)B * slots), ns(B), lpr(B);
+    const wa_scores rung_scores{lp.data(), ns.data(), lt.data(), lpr.data()};
+    for (;;) {  // the range tiers: a flagged rung restarts the ladder one tier up
+      bool overflow = false;
+      std::vector<uint8_t> frozen(B, 0);
+      int n_frozen = 0;
+      for (int r = 0; r < R && n_frozen < B && !overflow; ++r) {
+        for (int c = 0; c < B; ++c) {
+          temp[c] = fb->temperatures[r];
+          seed[c] = fb->seed[c] + (uint64_t)r;
+        }
+        m->frozen = r > 0 ? frozen.data() : nullptr;
+        WA_TRY(transcribe_once(m, mel_dev, B, lang_token, max_tokens, eot_stop, tok.data(), nt.data(), stream,
+                               &overflow, &rung_scores, r > 0));
+        if (overflow) break;
+        for (int c = 0; c < B; ++c) {
+          if (frozen[c]) continue;
+          std::memcpy(tokens_out + (size_t)c * max_tokens, tok.data() + (size_t)c * max_tokens, (size_t)max_tokens * 4);
+          n_tokens_out[c] = nt[c];
+          if (rung_out) rung_out[c] = r;
+          if (scores) {
+            if (scores->token_logprob)
+              std::memcpy(scores->token_logprob + c * slots, lp.data() + c * slots, slots * 4);
+            if (scores->no_speech_prob) scores->no_speech_prob[c] = ns[c];
+            if (scores->lang_token) scores->lang_token[c] = lt[c];
+            if (scores->lang_prob) scores->lang_prob[c] = lpr[c];
+          }
+          // the ladder rule: the mean of the stored log-probabilities below the
+          // threshold, unless the no-speech score calls the clip silence
+          // (comparisons with a NaN threshold are false: that test is off)
+          double sum = 0.0;
+          int cnt = 0;
+          for (size_t i = 0; i < slots; ++i) {
+            const float v = lp[c * slots + i];
+            if (!std::isnan(v)) {
+              sum += v;
+              ++cnt;
+            }
+          }
+          const double mean = cnt ? sum / cnt : 0.0;
+          const bool needs = mean < (double)fb->logprob_threshold && !(ns[c] > fb->no_speech_threshold);
+          if (!needs) {
+            frozen[c] = 1;
+            ++n_frozen;
+          }
+        }
+      }
+      if (!overflow) return WQ4_OK;
+      WA_TRY(raise_tier(m));
+    }
+  });
 }
 
 extern "C" {
@@ -809,64 +876,8 @@ wq4_status wa_transcribe_fallback(wa_model* m, const float* mel_dev, int n_clips
   if (bad_temperatures(fb->temperatures, fb->n_temperatures))
     return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
   if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  const int B = n_clips, R = fb->n_temperatures;
-  const size_t slots = (size_t)max_tokens + 1;
-  std::vector<float> temp(B);
-  std::vector<uint64_t> seed(B);
-  return with_sampling(m, temp.data(), seed.data(), fb->timestamps, fb->max_initial, [&]() -> wq4_status {
-    // one rung's results; the clips it was run for are copied to the caller's arrays
-    std::vector<int32_t> tok((size_t)B * max_tokens), nt(B), lt(B);
-    std::vector<float> lp((size_t)B * slots), ns(B), lpr(B);
-    const wa_scores rung_scores{lp.data(), ns.data(), lt.data(), lpr.data()};
-    for (;;) {  // the range tiers: a flagged rung restarts the ladder one tier up
-      bool overflow = false;
-      std::vector<uint8_t> frozen(B, 0);
-      int n_frozen = 0;
-      for (int r = 0; r < R && n_frozen < B && !overflow; ++r) {
-        for (int c = 0; c < B; ++c) {
-          temp[c] = fb->temperatures[r];
-          seed[c] = fb->seed[c] + (uint64_t)r;
-        }
-        m->frozen = r > 0 ? frozen.data() : nullptr;
-        WA_TRY(transcribe_once(m, mel_dev, B, lang_token, max_tokens, eot_stop, tok.data(), nt.data(), stream,
-                               &overflow, &rung_scores, r > 0));
-        if (overflow) break;
-        for (int c = 0; c < B; ++c) {
-          if (frozen[c]) continue;
-          std::memcpy(tokens_out + (size_t)c * max_tokens, tok.data() + (size_t)c * max_tokens, (size_t)max_tokens * 4);
-          n_tokens_out[c] = nt[c];
-          if (rung_out) rung_out[c] = r;
-          if (scores) {
-            if (scores->token_logprob)
-              std::memcpy(scores->token_logprob + c * slots, lp.data() + c * slots, slots * 4);
-            if (scores->no_speech_prob) scores->no_speech_prob[c] = ns[c];
-            if (scores->lang_token) scores->lang_token[c] = lt[c];
-            if (scores->lang_prob) scores->lang_prob[c] = lpr[c];
-          }
-          // the ladder rule: the mean of the stored log-probabilities below the
-          // threshold, unless the no-speech score calls the clip silence
-          // (comparisons with a NaN threshold are false: that test is off)
-          double sum = 0.0;
-          int cnt = 0;
-          for (size_t i = 0; i < slots; ++i) {
-            const float v = lp[c * slots + i];
-            if (!std::isnan(v)) {
-              sum += v;
-              ++cnt;
-            }
-          }
-          const double mean = cnt ? sum / cnt : 0.0;
-          const bool needs = mean < (double)fb->logprob_threshold && !(ns[c] > fb->no_speech_threshold);
-          if (!needs) {
-            frozen[c] = 1;
-            ++n_frozen;
-          }
-        }
-      }
-      if (!overflow) return WQ4_OK;
-      WA_TRY(raise_tier(m));
-    }
-  });
+  return transcribe_ladder(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, fb, tokens_out, n_tokens_out, scores,
+                           rung_out, stream);
 }
 
 wq4_status wa_sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out) {

@@ -52,6 +52,31 @@ class Fallback(ctypes.Structure):
                 ("max_initial", ctypes.c_int)]
 
 
+class LongOptions(ctypes.Structure):
+    """struct wa_long_options: one transcribe_long call's decode options."""
+
+    _fields_ = [("max_tokens", ctypes.c_int), ("max_windows", ctypes.c_int), ("lang_token", ctypes.c_int),
+                ("max_initial", ctypes.c_int), ("temperatures", ctypes.POINTER(ctypes.c_float)),
+                ("n_temperatures", ctypes.c_int), ("logprob_threshold", ctypes.c_float),
+                ("no_speech_threshold", ctypes.c_float), ("seed", ctypes.POINTER(ctypes.c_uint64))]
+
+
+class LongWindow(ctypes.Structure):
+    """struct wa_long_window: one decoded window of a recording."""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("stream", "index", "seek", "size", "advance", "skipped", "rung",
+                                               "lang_token", "n_tokens")] + \
+               [(n, ctypes.c_float) for n in ("temperature", "no_speech_prob", "lang_prob")] + \
+               [("avg_logprob", ctypes.c_double)]
+
+
+class LongSegment(ctypes.Structure):
+    """struct wa_long_segment: tokens [tok_begin, tok_end) of a window, in seconds of the recording."""
+
+    _fields_ = [("stream", ctypes.c_int32), ("window", ctypes.c_int32), ("tok_begin", ctypes.c_int32),
+                ("tok_end", ctypes.c_int32), ("start", ctypes.c_double), ("end", ctypes.c_double)]
+
+
 RULE_FIELDS = ("text_ok", "ts_lo", "ts_hi", "first", "last", "penult", "t_last", "pad")  # a rule record's 8 int32
 
 
@@ -162,6 +187,26 @@ def lib() -> ctypes.CDLL:
         for n in ("wa_transcribe_sampled", "wa_transcribe_batches_sampled", "wa_transcribe_fallback",
                   "wa_sample_noise", "wa_logits_sample_check", "wa_row_sample_check"):
             getattr(L, n).restype = c_int
+        i64p, cip = ctypes.POINTER(c_i64), ctypes.POINTER(c_int)
+        L.wa_long_mel_max.argtypes = [c_int, vp, c_int, i64p, i64p, c_int, vp, vp]
+        L.wa_long_mel_windows.argtypes = [c_int, vp, c_int, i64p, i64p, i32p, i32p, vp, c_int, vp, vp]
+        L.wa_long_advance.argtypes = [i32p, c_int, c_int, c_int, ctypes.c_float, ctypes.c_double, ctypes.c_float,
+                                      ctypes.c_float, cip, cip]
+        L.wa_long_round.argtypes = [i32p, i32p, i32p, c_int, c_int, c_int, cip, cip]
+        L.wa_transcribe_long.argtypes = [vp, vp, c_int, i64p, i64p, ctypes.POINTER(LongOptions), ctypes.POINTER(vp),
+                                         vp]
+        L.wa_long_result_free.argtypes = [vp]
+        L.wa_long_result_free.restype = None
+        L.wa_long_result_streams.argtypes = [vp]
+        L.wa_long_result_max_tokens.argtypes = [vp]
+        L.wa_long_result_stream.argtypes = [vp, c_int, cip, cip, cip]
+        L.wa_long_result_windows.argtypes = [vp, c_int, ctypes.POINTER(LongWindow), c_int, cip]
+        L.wa_long_result_window.argtypes = [vp, c_int, c_int, i32p, c_int, cip, f32p, c_int]
+        L.wa_long_result_segments.argtypes = [vp, c_int, ctypes.POINTER(LongSegment), c_int, cip]
+        for n in ("wa_long_mel_max", "wa_long_mel_windows", "wa_long_advance", "wa_long_round", "wa_transcribe_long",
+                  "wa_long_result_streams", "wa_long_result_max_tokens", "wa_long_result_stream",
+                  "wa_long_result_windows", "wa_long_result_window", "wa_long_result_segments"):
+            getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
                   "wa_last_pipeline_stats", "wa_last_timings", "wa_encode",
@@ -228,6 +273,82 @@ def log_mel(audio, n_mels: int = 128, n_samples: Optional[int] = None, out=None)
                            ctypes.c_void_p(out.data_ptr()),
                            ctypes.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)))
     return out
+
+
+def _i64(a):
+    return np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1))
+
+
+def _i32(a):
+    return np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
+
+
+def _as(a, ctype):
+    return a.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+def long_mel_max(audio, offset, n_samples, n_mels: int = 128, out=None):
+    """The recording maxima of long-form windows (wa_long_mel_max): audio a cuda
+    f32 buffer holding every recording, recording r its n_samples[r] samples
+    from element offset[r] -> cuda f32 [len(offset)], max(-10, the largest raw
+    log-mel value of the recording)."""
+    torch = _torch()
+    assert audio.dtype == torch.float32 and audio.is_cuda and audio.is_contiguous()
+    off, n = _i64(offset), _i64(n_samples)
+    assert off.size == n.size and (off.size == 0 or int((off + n).max()) <= audio.numel())
+    if out is None:
+        out = torch.empty(off.size, device=audio.device, dtype=torch.float32)
+    check(lib().wa_long_mel_max(_dev(audio), _ptr(audio), int(off.size), _as(off, ctypes.c_int64),
+                                _as(n, ctypes.c_int64), n_mels, _ptr(out),
+                                ctypes.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)))
+    return out
+
+
+def long_mel_windows(audio, offset, n_samples, seek, max_index, max_dev, n_mels: int = 128, out=None):
+    """Windows of long recordings (wa_long_mel_windows): clip c is the 3000
+    frames from mel frame seek[c] of the recording (offset[c], n_samples[c])
+    in the cuda f32 buffer `audio`, normalised against max_dev[max_index[c]]
+    (long_mel_max), exact zeros past the recording's n_samples // 160 content
+    frames -> cuda f32 [len(seek), n_mels, 3000], the transcribe input."""
+    torch = _torch()
+    assert audio.dtype == torch.float32 and audio.is_cuda and audio.is_contiguous()
+    assert max_dev.dtype == torch.float32 and max_dev.is_cuda and max_dev.is_contiguous()
+    off, n, sk, mi = _i64(offset), _i64(n_samples), _i32(seek), _i32(max_index)
+    B = int(sk.size)
+    assert off.size == B and n.size == B and mi.size == B
+    assert B == 0 or (int((off + n).max()) <= audio.numel() and int(mi.max()) < max_dev.numel())
+    if out is None:
+        out = torch.empty((B, n_mels, MEL_FRAMES), device=audio.device, dtype=torch.float32)
+    check(lib().wa_long_mel_windows(_dev(audio), _ptr(audio), B, _as(off, ctypes.c_int64), _as(n, ctypes.c_int64),
+                                    _as(sk, ctypes.c_int32), _as(mi, ctypes.c_int32), _ptr(max_dev), n_mels,
+                                    _ptr(out), ctypes.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)))
+    return out
+
+
+def long_advance(tokens, ts0: int, size: int, no_speech_prob: float, avg_logprob: float,
+                 logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6):
+    """The skip and advance rules of one long-form window (wa_long_advance; host
+    only) -> (skipped, advance in mel frames).  None switches a threshold off."""
+    toks = _i32(tokens)
+    nan = float("nan")
+    sk, adv = ctypes.c_int(), ctypes.c_int()
+    check(lib().wa_long_advance(_as(toks, ctypes.c_int32), int(toks.size), int(ts0), int(size), float(no_speech_prob),
+                                float(avg_logprob), nan if logprob_threshold is None else float(logprob_threshold),
+                                nan if no_speech_threshold is None else float(no_speech_threshold),
+                                ctypes.byref(sk), ctypes.byref(adv)))
+    return bool(sk.value), int(adv.value)
+
+
+def long_round(content_frames, seek, windows, max_batch: int, max_windows: int) -> list[int]:
+    """The recordings of the next long-form round (wa_long_round; host only):
+    in index order those with seek < content_frames and windows < max_windows,
+    up to max_batch of them."""
+    c, s, w = _i32(content_frames), _i32(seek), _i32(windows)
+    assert c.size == s.size == w.size
+    out, n = (ctypes.c_int * max(1, int(max_batch)))(), ctypes.c_int()
+    check(lib().wa_long_round(_as(c, ctypes.c_int32), _as(s, ctypes.c_int32), _as(w, ctypes.c_int32), int(c.size),
+                              int(max_batch), int(max_windows), out, ctypes.byref(n)))
+    return [int(out[i]) for i in range(n.value)]
 
 
 def xattn_check(q, wk_raw, wv_raw, bv, enc, Tq: int, H: int, weight_type: int = 0,
@@ -730,6 +851,78 @@ class WhisperModel:
         clips = self._scored(mel, None, lang_token, max_tokens, eot_stop, max_initial,
                              fallback=(temperatures, logprob_threshold, no_speech_threshold, seed, timestamps))
         return self._timestamped(clips) if timestamps else clips
+
+    def transcribe_long(self, audio, n_samples=None, seed=0, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+                        logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+                        lang_token: Optional[int] = 50259, max_tokens: int = 224, max_windows: int = 1 << 20,
+                        max_initial: int = 50) -> list[dict]:
+        """Long-form transcription (wa_transcribe_long): OpenAI transcribe()'s
+        loop -- the window at seek, timestamp decode with the temperature
+        ladder, the silence skip, segments in absolute seconds, seek advanced
+        to the last closed timestamp -- over many recordings at once, batches
+        filled across recordings.  audio: a list of 1-D cuda f32 tensors (16
+        kHz mono), or a 2-D tensor whose row r holds n_samples[r] samples
+        (default: the whole row).  seed: one per recording, or one for all;
+        window w of a recording decodes with seed + 8 w.  None switches a
+        threshold off.  Per recording a dict: "windows", each the dict of
+        transcribe_fallback's clip plus seek, size, advance (mel frames) and
+        skipped; "segments", (start_s, end_s, tokens) in seconds of the
+        recording; "truncated", whether max_windows ended it early."""
+        torch = _torch()
+        if isinstance(audio, (list, tuple)):
+            assert n_samples is None and all(a.dim() == 1 for a in audio)
+            n = _i64([a.numel() for a in audio])
+            off = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+            buf = torch.cat([a.reshape(-1) for a in audio]) if len(audio) > 1 else audio[0].contiguous()
+            if buf.numel() == 0:
+                buf = torch.zeros(1, device=buf.device, dtype=torch.float32)
+        else:
+            assert audio.dim() == 2
+            buf = audio if audio.stride(1) == 1 and audio.numel() else audio.contiguous()
+            S, L = buf.shape
+            n = np.full(S, L, np.int64) if n_samples is None else np.broadcast_to(_i64(n_samples), (S,)).copy()
+            assert int(n.max()) <= L
+            off = np.arange(S, dtype=np.int64) * buf.stride(0)
+        assert buf.dtype == torch.float32 and buf.is_cuda
+        S = int(n.size)
+        tl = np.ascontiguousarray(np.asarray(temperatures, np.float32).reshape(-1))
+        _, sd = _sampling_arrays(0.0, seed, S)
+        nan = float("nan")
+        opt = LongOptions(int(max_tokens), int(max_windows), -1 if lang_token is None else int(lang_token),
+                          int(max_initial), _as(tl, ctypes.c_float), int(tl.size),
+                          nan if logprob_threshold is None else float(logprob_threshold),
+                          nan if no_speech_threshold is None else float(no_speech_threshold),
+                          _as(sd, ctypes.c_uint64))
+        h = ctypes.c_void_p(None)
+        check(lib().wa_transcribe_long(self._h, _ptr(buf), S, _as(off, ctypes.c_int64), _as(n, ctypes.c_int64),
+                                       ctypes.byref(opt), ctypes.byref(h), self._stream()))
+        try:
+            return [self._long_stream(h, r, max_tokens) for r in range(S)]
+        finally:
+            lib().wa_long_result_free(h)
+
+    @staticmethod
+    def _long_stream(h, r: int, max_tokens: int) -> dict:
+        L = lib()
+        nw, tr, nsg = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        check(L.wa_long_result_stream(h, r, ctypes.byref(nw), ctypes.byref(tr), ctypes.byref(nsg)))
+        wins = (LongWindow * max(1, nw.value))()
+        segs = (LongSegment * max(1, nsg.value))()
+        check(L.wa_long_result_windows(h, r, wins, nw.value, ctypes.byref(nw)))
+        check(L.wa_long_result_segments(h, r, segs, nsg.value, ctypes.byref(nsg)))
+        windows = []
+        for i in range(nw.value):
+            w = wins[i]
+            toks, lp, nt = np.zeros(max_tokens, np.int32), np.zeros(max_tokens + 1, np.float32), ctypes.c_int()
+            check(L.wa_long_result_window(h, r, i, _as(toks, ctypes.c_int32), max_tokens, ctypes.byref(nt),
+                                          _as(lp, ctypes.c_float), max_tokens + 1))
+            clip = _scored_clip(toks, nt.value, lp, w.no_speech_prob, w.lang_token, w.lang_prob)
+            clip.update(avg_logprob=float(w.avg_logprob), rung=int(w.rung), temperature=float(w.temperature),
+                        seek=int(w.seek), size=int(w.size), advance=int(w.advance), skipped=bool(w.skipped))
+            windows.append(clip)
+        segments = [(float(s.start), float(s.end), windows[s.window]["tokens"][s.tok_begin:s.tok_end])
+                    for s in segs[:nsg.value]]
+        return {"windows": windows, "segments": segments, "truncated": bool(tr.value)}
 
     def _scored(self, mels, NB: Optional[int], lang_token, max_tokens: int, eot_stop: bool,
                 max_initial: Optional[int] = None, sampling=None, fallback=None):
