@@ -133,6 +133,70 @@ wq4_status wa_self_attention_check(int device, const float* qkv_dev, float* cach
   });
 }
 
+wq4_status wa_conv_gelu_check(int device, const float* in_dev, int64_t in_bs, int64_t in_cs, int64_t in_ts, int B,
+                              int C, int T_in, int stride, const float* w_dev, const float* bias_dev,
+                              const float* pos_dev, int N, float* out_dev) {
+  if (!in_dev || !w_dev || !bias_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");
+  if (B < 1 || C < 1 || T_in < 1 || N < 1 || (stride != 1 && stride != 2)) return fail(WQ4_EINVAL, "bad sizes");
+  if (C % 4 != 0) return fail(WQ4_EINVAL, "C must be a multiple of 4");
+  if (in_bs < 0 || in_cs < 1 || in_ts < 1) return fail(WQ4_EINVAL, "bad strides");
+  // channel-contiguous input: the kernel loads 4 channels as one 16-byte vector
+  if (in_cs == 1 && (in_ts % 4 != 0 || in_bs % 4 != 0))
+    return fail(WQ4_EINVAL, "a channel-contiguous input needs time and clip strides that are multiples of 4");
+  const int T_out = (T_in - 1) / stride + 1;
+  if ((int64_t)B * T_out > 2147483647LL - 128 || (int64_t)N * C > 2147483647LL / 3)
+    return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  const size_t nw = (size_t)N * C * 3;
+  std::vector<float> w(nw);
+  WA_HIP(hipMemcpy(w.data(), w_dev, nw * 4, hipMemcpyDeviceToHost));
+  const std::vector<float> wt = conv_weight_im2col(w.data(), N, C);
+  auto* wt_dev = d.alloc<float>(nw);
+  if (!wt_dev) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemcpy(wt_dev, wt.data(), nw * 4, hipMemcpyHostToDevice));
+  WA_HIP(launch_conv_gelu(in_dev, (long)in_bs, (long)in_cs, (long)in_ts, B, C, T_in, stride, wt_dev, bias_dev, pos_dev,
+                          N, out_dev, nullptr));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+wq4_status wa_embed_check(int device, const int32_t* tokens, const float* tok_emb_dev, int V,
+                          const float* pos_emb_dev, int ctx, int B, int Tq, int D, int pos0, int use_state,
+                          const float* gamma_dev, wq4_precision prec, float* x_dev, void* tiled_dev,
+                          float* stats_dev) {
+  if (!tokens || !tok_emb_dev || !pos_emb_dev || !x_dev) return fail(WQ4_EINVAL, "null argument");
+  if (gamma_dev && (!tiled_dev || !stats_dev)) return fail(WQ4_EINVAL, "gamma needs the operand and statistics outputs");
+  if (B < 1 || Tq < 1 || D < 1 || V < 1 || ctx < 1 || (int64_t)B * Tq > 2147483647LL)
+    return fail(WQ4_EINVAL, "bad sizes");
+  if (gamma_dev && D % 32 != 0) return fail(WQ4_EINVAL, "the folded form needs D % 32 == 0");
+  if (pos0 < 0 || (int64_t)pos0 + Tq > ctx) return fail(WQ4_EINVAL, "need 0 <= pos0 and pos0 + Tq <= ctx");
+  const int R = B * Tq;
+  for (int i = 0; i < R; ++i)
+    if (tokens[i] < 0 || tokens[i] >= V) return fail(WQ4_EINVAL, "token id outside [0, V)");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  auto* tok = d.alloc<int>(R);
+  if (!tok) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemcpy(tok, tokens, (size_t)R * 4, hipMemcpyHostToDevice));
+  // through the device state the host position is a value no row may use
+  DecodeState* st = nullptr;
+  if (use_state) {
+    st = d.alloc<DecodeState>(1);
+    if (!st) return fail(WQ4_ENOMEM, "allocation failed");
+    const DecodeState s0{pos0, 0, 0, 0};
+    WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  }
+  const int pos0_host = use_state ? -1 : pos0;
+  if (gamma_dev)
+    WA_HIP(launch_embed_fold(tok, tok_emb_dev, pos_emb_dev, B, Tq, D, st, pos0_host, x_dev, gamma_dev,
+                             static_cast<_Float16*>(tiled_dev), stats_dev, planes(prec), nullptr));
+  else
+    WA_HIP(launch_embed(tok, tok_emb_dev, pos_emb_dev, B, Tq, D, st, pos0_host, x_dev, nullptr));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
 // The fused pick on caller data, in the mode the arguments select (PickArgs):
 // wa_logits_argmax_check; with logprob_dev the scored launch of
 // wa_logits_logprob_check; with rules_host (n_clips records) the timestamp

@@ -830,9 +830,9 @@ hipError_t launch_embed(const int* tokens, const float* tok_emb, const float* po
 
 // Embedding + the LayerNorm-fold producer of the first decoder layer's
 // attn_ln (wq4_gemm_tiled_lnfold): x rows as embed_kernel, plus the A-tiled
-// operand of x * gamma and per (row, 32-column tile) the tile mean and sum
+// operand of x * gamma and per (row, 16-column tile) the tile mean and sum
 // of squared deviations.  One workgroup per row; thread t owns the float4 at
-// columns 4 t + 1024 i, so a tile is 8 consecutive lanes.
+// columns 4 t + 1024 i, so a tile is 4 consecutive lanes.
 template <int NS>
 __global__ __launch_bounds__(256) void embed_fold_kernel(const int* __restrict__ tokens, const float* __restrict__ te,
                                                          const float* __restrict__ pe, int Tq, int D,

@@ -111,7 +111,8 @@ hipError_t launch_embed(const int* tokens, const float* tok_emb, const float* po
                         const DecodeState* state, int pos0_host, float* x, hipStream_t st);
 
 // launch_embed + the LayerNorm-fold producer for gamma (wq4_gemm_tiled_lnfold):
-// also writes at = A-tiled x * gamma and stats [rows][D/32][2]; D % 32 == 0.
+// also writes at = A-tiled x * gamma and stats [rows][D/16][2] (mean and sum
+// of squared deviations of each 16-column tile of x); D % 32 == 0.
 hipError_t launch_embed_fold(const int* tokens, const float* tok_emb, const float* pos_emb, int B, int Tq, int D,
                              const DecodeState* state, int pos0_host, float* x, const float* gamma, _Float16* at,
                              float* stats, int ns, hipStream_t st);

@@ -350,6 +350,9 @@ struct Source {
 };
 std::unique_ptr<Source> synth_source(uint64_t seed);
 std::unique_ptr<Source> gguf_source(const GgufFile& f);
+// conv weight [N][C][3] (the reference's layout, loader.rs:254-268) ->
+// launch_conv_gelu's [N][kk*C + c] (im2col order, layers.rs:118-121)
+std::vector<float> conv_weight_im2col(const float* w, int N, int C);
 wq4_status build_model(wa_model* m, Source& src);
 wq4_status build_ln_fold(wa_model* m);
 

@@ -221,11 +221,7 @@ struct Builder {
   // [N][kk*C + c] (im2col order, layers.rs:118-121)
   float* conv(const std::string& name, int N, int C) {
     auto w = get(name, (int64_t)N * C * 3, -lin_scale(3 * C), lin_scale(3 * C));
-    std::vector<float> t((size_t)N * 3 * C);
-    for (int n = 0; n < N; ++n)
-      for (int c = 0; c < C; ++c)
-        for (int kk = 0; kk < 3; ++kk) t[(size_t)n * 3 * C + kk * C + c] = w[((size_t)n * C + c) * 3 + kk];
-    return upload(t);
+    return upload(conv_weight_im2col(w.data(), N, C));
   }
 };
 
@@ -242,6 +238,14 @@ Config preset(int variant) {
     default:  // parity-test configuration (not a released model)
       return {80, 1500, 384, 6, 2, 448, 384, 6, 2, 51866, 100};
   }
+}
+
+std::vector<float> conv_weight_im2col(const float* w, int N, int C) {
+  std::vector<float> t((size_t)N * 3 * C);
+  for (int n = 0; n < N; ++n)
+    for (int c = 0; c < C; ++c)
+      for (int kk = 0; kk < 3; ++kk) t[(size_t)n * 3 * C + kk * C + c] = w[((size_t)n * C + c) * 3 + kk];
+  return t;
 }
 
 std::unique_ptr<Source> synth_source(uint64_t seed) { return std::make_unique<SynthSource>(seed); }

@@ -151,7 +151,13 @@ def lib() -> ctypes.CDLL:
         L.wa_encoder_attention_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, vp]
         L.wa_self_attention_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
         L.wa_logits_argmax_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
-        sp = ctypes.POINTER(Scores)
+        L.wa_conv_gelu_check.argtypes = [c_int, vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, vp, vp, vp, c_int,
+                                         vp]
+        L.wa_embed_check.argtypes = [c_int, i32p, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, c_int,
+                                     vp, vp, vp]
+        for n in ("wa_conv_gelu_check", "wa_embed_check"):
+            getattr(L, n).restype = c_int
+        sp =ctypes.POINTER(Scores)
         L.wa_transcribe_scored.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
         L.wa_transcribe_batches_scored.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
         L.wa_logits_logprob_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp]
@@ -443,6 +449,56 @@ def encoder_attention_check(qkv, T: int, H: int, precision: int = wq4.PREC_F16X2
     out = torch.empty((B * T, 64 * H), device=qkv.device, dtype=torch.float32)
     check(lib().wa_encoder_attention_check(_dev(qkv), _ptr(qkv), B, T, H, precision, _ptr(out)))
     return out
+
+
+def conv_gelu_check(x, w, bias, stride: int, pos=None, out=None):
+    """The conv stem's kernel (wa_conv_gelu_check): x cuda f32 of logical shape
+    [B, C, T_in] in any element strides (x.stride(): channel-major as the mel,
+    or a permuted [B, T_in, C] as conv1's output), w cuda f32 [N, C, 3], bias
+    [N], pos [T_out, N] or None -> [B, T_out, N] = gelu(conv1d(x) + bias)
+    (+ pos), padding 1."""
+    torch = _torch()
+    B, C, T_in = x.shape
+    N = w.shape[0]
+    assert tuple(w.shape) == (N, C, 3)
+    T_out = (T_in - 1) // stride + 1
+    if out is None:
+        out = torch.empty((B, T_out, N), device=x.device, dtype=torch.float32)
+    bs, cs, ts = x.stride()
+    w, bias = w.contiguous(), bias.contiguous()
+    pos = None if pos is None else pos.contiguous()
+    check(lib().wa_conv_gelu_check(_dev(x), _ptr(x), bs, cs, ts, B, C, T_in, stride, _ptr(w), _ptr(bias),
+                                   None if pos is None else _ptr(pos), N, _ptr(out)))
+    return out
+
+
+def embed_check(tokens, tok_emb, pos_emb, B: int, Tq: int, pos0: int, use_state: bool = False, gamma=None,
+                precision: int = wq4.PREC_F16X2, x=None, tiled=None, stats=None):
+    """The decoder's embedding kernels (wa_embed_check): tokens host int32
+    [B * Tq], tok_emb cuda f32 [V, D], pos_emb cuda f32 [ctx, D] -> x
+    [B * Tq, D]; the position reaches the kernel from the host or, with
+    use_state, from a device-resident decode state.  With gamma (cuda f32 [D])
+    the LayerNorm-fold producer form: also (tiled, stats) = the A-tiled operand
+    bytes of x * gamma and the 16-column tile statistics [B * Tq, D / 16, 2].
+    x / tiled / stats: caller-allocated outputs (guarded buffers)."""
+    torch = _torch()
+    V, D = tok_emb.shape
+    ctx = pos_emb.shape[0]
+    tokens = np.ascontiguousarray(tokens, np.int32)
+    assert tokens.size == B * Tq and tok_emb.is_contiguous() and pos_emb.is_contiguous()
+    R = B * Tq
+    if x is None:
+        x = torch.empty((R, D), device=tok_emb.device, dtype=torch.float32)
+    if gamma is not None:
+        if tiled is None:
+            tiled = torch.zeros(wq4.lib().wq4_atiled_bytes(R, D, precision), device=tok_emb.device, dtype=torch.uint8)
+        if stats is None:
+            stats = torch.empty((R, D // 16, 2), device=tok_emb.device, dtype=torch.float32)
+    check(lib().wa_embed_check(_dev(tok_emb), tokens.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(tok_emb), V,
+                               _ptr(pos_emb), ctx, B, Tq, D, pos0, 1 if use_state else 0,
+                               None if gamma is None else _ptr(gamma), precision, _ptr(x),
+                               None if gamma is None else _ptr(tiled), None if gamma is None else _ptr(stats)))
+    return x, tiled, stats
 
 
 def self_attention_check(qkv, cache_k, cache_v, Tq: int, H: int, kv_len: int, precision: int = wq4.PREC_F16X2):
