@@ -262,3 +262,35 @@ def test_pipelined_batches_recover_through_the_tiers(tmp_path):
     assert m.range_tier == 3
     assert out == [tv, tv]
     m.close()
+
+
+@pytest.mark.gpu
+def test_sampled_batches_rerun_with_their_own_temperatures_and_seeds(tmp_path):
+    """wa_transcribe_batches_sampled on the fc1 stress model, 2 batches of 2
+    clips, 6 tokens, a temperature and a seed of its own per clip: batch 0 flags
+    in the pipeline and goes through the tiers to tier 2, batch 1 is re-run
+    there -- each re-run must draw with its own batch's slice of the per-clip
+    arrays.  Tokens and log-probability slots equal, bit for bit, those of one
+    wa_transcribe_sampled per batch with that slice, on the model now at tier 2
+    (the same kernels on the same inputs)."""
+    import torch
+
+    import whisper_amd
+
+    NB, B, n = 2, 2, 6
+    m = whisper_amd.WhisperModel.from_gguf(_write("fc1", tmp_path), "tiny_test", max_batch=B)
+    n_mels = m.config["n_mels"]
+    x = torch.from_numpy(np.stack([np.stack([wo.synthetic_mel(i * B + c, n_mels) for c in range(B)])
+                                   for i in range(NB)])).cuda()
+    temps = np.array([[0.3, 0.7], [1.0, 0.5]], np.float32)
+    seeds = np.array([[11, 22], [33, 44]], np.uint64)
+    assert m.range_tier == 0
+    got = m.transcribe_batches_sampled(x, temps, seeds, 50259, max_tokens=n, eot_stop=False)
+    assert m.range_tier == 2  # raised inside the call: every batch was re-run
+    for i in range(NB):
+        one = m.transcribe_sampled(x[i], temps[i], seeds[i], 50259, max_tokens=n, eot_stop=False)
+        assert m.range_tier == 2
+        for a, b in zip(got[i], one):
+            assert a["tokens"] == b["tokens"] and len(a["tokens"]) > 0, (i, a["tokens"], b["tokens"])
+            assert np.array_equal(a["logprob_slots"], b["logprob_slots"], equal_nan=True), i
+    m.close()

@@ -78,6 +78,29 @@ def test_transcribe_batches_scored_rejects_bad_arguments():
     assert "max_tokens" in L.wa_last_error().decode()
 
 
+def test_plain_entries_check_in_the_same_order():
+    """wa_transcribe and wa_transcribe_batches check like the scored entries:
+    null pointers, n_batches, max_tokens, and the clip count -- the only read of
+    the model, which here is a block of zero bytes -- last of all."""
+    L = whisper_amd.lib()
+    model, mel, tok, nt = _bufs()
+    vp = ctypes.c_void_p
+    addr = lambda b: vp(ctypes.addressof(b))
+    err = lambda: L.wa_last_error().decode()
+    f, g = L.wa_transcribe, L.wa_transcribe_batches
+    assert f(None, addr(mel), 1, 50259, 8, 1, tok, nt, None) == EINVAL and "null" in err()
+    assert f(addr(model), None, 1, 50259, 8, 1, tok, nt, None) == EINVAL and "null" in err()
+    assert g(None, addr(mel), 2, 1, 50259, 8, 1, tok, nt, None) == EINVAL and "null" in err()
+    assert g(addr(model), addr(mel), 0, 1, 50259, 8, 1, tok, nt, None) == EINVAL and "n_batches" in err()
+    for mt in (0, 225):
+        # n_clips = 1 is out of the zero model's range too: max_tokens is reported
+        assert f(addr(model), addr(mel), 1, 50259, mt, 1, tok, nt, None) == EINVAL and "max_tokens" in err()
+        assert g(addr(model), addr(mel), 2, 1, 50259, mt, 1, tok, nt, None) == EINVAL and "max_tokens" in err()
+        assert g(addr(model), addr(mel), 0, 1, 50259, mt, 1, tok, nt, None) == EINVAL and "n_batches" in err()
+    assert f(addr(model), addr(mel), 1, 50259, 8, 1, tok, nt, None) == EINVAL and "n_clips" in err()
+    assert g(addr(model), addr(mel), 2, 1, 50259, 8, 1, tok, nt, None) == EINVAL and "n_clips" in err()
+
+
 def test_logits_logprob_check_rejects_bad_arguments():
     L = whisper_amd.lib()
     buf = (ctypes.c_float * 64)()

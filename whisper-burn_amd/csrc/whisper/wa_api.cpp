@@ -186,7 +186,7 @@ wq4_status wa_prompt_logits(wa_model* m, const int32_t* prompt_dev, int n_clips,
   g.nb = n_clips;
   g.xres = xattn_residency(n_clips, m->cfg.n_audio_ctx, m->ns, m->cfg.n_audio_state);
   g.xplan = xattn_plan(m->cfg.n_audio_ctx, n_clips);
-  WA_TRY(decoder_forward(m, g, prompt_dev, plen, nullptr, 0, 0, st));
+  WA_TRY(decoder_forward(m, g, DecodeCall(), prompt_dev, plen, nullptr, 0, 0, st));
   WA_HIP(hipMemcpyAsync(logits_dev, g.logits, (size_t)n_clips * m->cfg.n_vocab * 4, hipMemcpyDeviceToDevice, st));
   return WQ4_OK;
 }

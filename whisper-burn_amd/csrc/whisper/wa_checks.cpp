@@ -93,6 +93,11 @@ long long wa_decode_graph_key(const wa_model* m, int group) {
   return m->groups[group].graph_key;
 }
 
+long long wa_decode_graph_key_check(int mode, int lane, int b0, int nb, int eot, int trace, int group_kv,
+                                    int range_tier, int splits, int residency) {
+  return graph_key(mode, lane, b0, nb, eot, trace, group_kv, range_tier, splits, residency);
+}
+
 wq4_status wa_xattn_kv_check(int device, const float* q_dev, const float* k_dev, const float* v_dev, int n_clips,
                              int Tq, int T, int H, wq4_precision prec, float* out_dev) {
   if (!q_dev || !k_dev || !v_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");

@@ -76,40 +76,40 @@ bool fused_pick(const DecGroup& g, int Tq, const DecodeState* state) {
   return state != nullptr && Tq == 1 && g.nb <= 32;
 }
 
-// The fused pick of group g in the model's mode: a scored transcribe
-// (m->score) leaves the pick's log-probability in next_lp, a timestamp one
-// (m->ts) picks under the clips' rule records, a sampled one (m->sample) at
-// their temperatures and seeds.
-PickArgs pick_args(const wa_model* m, const DecGroup& g) {
+// The fused pick of group g in the call's mode: a scored call (call.score)
+// leaves the pick's log-probability in next_lp, a timestamp one (call.ts)
+// picks under the clips' rule records, a sampled one (call.sample) at their
+// temperatures and seeds.
+PickArgs pick_args(const wa_model* m, const DecGroup& g, const DecodeCall& call) {
   PickArgs p{};
   p.scratch = g.lg_scr;
   p.counter = g.lg_ctr;
   p.out_tok = g.next_tok;
-  p.out_lp = m->score ? g.next_lp : nullptr;
-  p.rules = m->ts ? g.ts_rules : nullptr;
+  p.out_lp = call.score ? g.next_lp : nullptr;
+  p.rules = call.ts ? g.ts_rules : nullptr;
   p.ts0 = m->ts0();
-  p.temp = m->sample ? g.smp_temp : nullptr;
-  p.seed = m->sample ? g.smp_seed : nullptr;
+  p.temp = call.sample ? g.smp_temp : nullptr;
+  p.seed = call.sample ? g.smp_seed : nullptr;
   return p;
 }
 
 // One greedy step (whisper.rs:104-125): bookkeeping, decode_step, the pick.
-// The bookkeeping stores a scored transcribe's log-probabilities where the
-// tokens go and advances a timestamp transcribe's rule records; a
-// stored-logits group picks with the row kernels, in the mode of pick_args.
-wq4_status decode_step(wa_model* m, DecGroup& g, int eot_stop, hipStream_t st) {
-  const PickArgs p = pick_args(m, g);
+// The bookkeeping stores a scored call's log-probabilities where the tokens
+// go and advances a timestamp call's rule records; a stored-logits group
+// picks with the row kernels, in the mode of pick_args.
+wq4_status decode_step(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st) {
+  const PickArgs p = pick_args(m, g, call);
   const int V = m->cfg.n_vocab;
-  WA_HIP(launch_bookkeep(g.next_tok, p.out_lp, g.tokens, m->score ? g.logprob : nullptr, g.ntok, g.done, g.nb,
-                         kMaxTokens, eot_stop, g.state, m->ts ? g.ts_rules : nullptr, p.ts0, V, st));
-  WA_TRY(decoder_forward(m, g, g.next_tok, 1, g.state, 0, 0, st));
+  WA_HIP(launch_bookkeep(g.next_tok, p.out_lp, g.tokens, call.score ? g.logprob : nullptr, g.ntok, g.done, g.nb,
+                         kMaxTokens, call.eot_stop, g.state, call.ts ? g.ts_rules : nullptr, p.ts0, V, st));
+  WA_TRY(decoder_forward(m, g, call, g.next_tok, 1, g.state, 0, 0, st));
   if (fused_pick(g, 1, g.state)) return WQ4_OK;
   if (p.temp || p.rules) {  // the sampled (pick step + 1) or timestamp pick over the stored rows
     WA_HIP(launch_row_pick(g.logits, g.nb, V, V, 0, kMinTokens, g.state, p.rules, p.ts0, p.temp, p.seed, 0, g.next_tok,
                            g.next_lp, nullptr, m->range_flag, st));
   } else {
     WA_HIP(launch_argmax_step(g.logits, g.nb, V, kMinTokens, g.state, g.next_tok, m->range_flag, st));
-    if (m->score)
+    if (call.score)
       WA_HIP(launch_row_logprob(g.logits, g.nb, V, 0, V, 0, kMinTokens, g.state, g.next_tok, 1, 0, g.next_lp, 1, st));
   }
   return WQ4_OK;
@@ -366,9 +366,10 @@ wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches, int
 
 // Decoder pass over Tq new tokens for the clips of group g (forward_prompt
 // when state == nullptr, decode_step otherwise), ending in last-position
-// logits.  Self-KV and the encoder planes are addressed at the group's clip offset.
-wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, const DecodeState* state, int pos0,
-                           int kv0, hipStream_t st) {
+// logits.  Self-KV and the encoder planes are addressed at the group's clip
+// offset.  The call decides the fused pick's mode and the trace, nothing else.
+wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, const int* tokens, int Tq,
+                           const DecodeState* state, int pos0, int kv0, hipStream_t st) {
   const Config& c = m->cfg;
   const int D = c.n_text_state, H = c.n_text_head, T = c.n_audio_ctx;
   const int B = g.nb;
@@ -456,11 +457,11 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, 
     // the final LN writes the pick's operand directly (A-tiled, the
     // embedding planes' precision)
     WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, m->prec, g.hid_t, nullptr, st));
-    const size_t tofs = (size_t)g.b0 * m->trace_s1 * m->trace_k;
-    WA_HIP(launch_logits_pick(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, pick_args(m, g),
-                              m->trace_out ? m->trace_ids + tofs : nullptr,
-                              m->trace_out ? m->trace_out + tofs : nullptr, m->trace_s1, m->trace_k, m->range_flag,
-                              st));
+    const size_t tofs = (size_t)g.b0 * call.trace_s1 * call.trace_k;
+    WA_HIP(launch_logits_pick(g.hid_t, B, D, m->tok_emb2, m->ns, c.n_vocab, kMinTokens, state, pick_args(m, g, call),
+                              call.trace_out ? call.trace_ids + tofs : nullptr,
+                              call.trace_out ? call.trace_out + tofs : nullptr, call.trace_s1, call.trace_k,
+                              m->range_flag, st));
     return WQ4_OK;
   }
   WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, WQ4_PREC_F16X2, nullptr, g.hid, st));
@@ -493,11 +494,11 @@ static wq4_status score_sot(wa_model* m, DecGroup& g, const float* z0, const int
 
 // Prompt of group g (whisper.rs:60-99), leaving the first greedy token in
 // next_tok and the DecodeState ready for the step graph.
-wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st) {
+wq4_status prompt_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st) {
   const Config& c = m->cfg;
-  const int B = g.nb;
+  const int B = g.nb, lang_token = call.lang_token;
   // a timestamp transcribe's prompt ends at TRANSCRIBE: no NO_TIMESTAMPS
-  const int tail = m->ts ? 1 : 2;  // prompt tokens after the language token
+  const int tail = call.ts ? 1 : 2;  // prompt tokens after the language token
   std::vector<int> ptok((size_t)B * 4);
   int pos0, kv0;
   if (lang_token >= 0) {
@@ -506,11 +507,11 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
       ptok[b * plen + 0] = kSOT;
       ptok[b * plen + 1] = lang_token;
       ptok[b * plen + 2] = c.transcribe_token();
-      if (!m->ts) ptok[b * plen + 3] = c.no_timestamps_token();
+      if (!call.ts) ptok[b * plen + 3] = c.no_timestamps_token();
     }
     WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * plen * 4, hipMemcpyHostToDevice, st));
-    WA_TRY(decoder_forward(m, g, g.prompt_tok, plen, nullptr, 0, 0, st));
-    if (m->score) {
+    WA_TRY(decoder_forward(m, g, call, g.prompt_tok, plen, nullptr, 0, 0, st));
+    if (call.score) {
       // z0, the SOT position's logits: row 0 of each clip's final-LN rows in
       // g.hid (by causality the single-SOT pass of the auto-detect prompt)
       WA_HIP(launch_logits(g.hid, B, c.n_text_state, (int64_t)plen * c.n_text_state, m->tok_emb, c.n_vocab, g.z0, st));
@@ -525,52 +526,52 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
     for (int b = 0; b < B; ++b) {
       ptok[b * plen + 0] = kSOT;
       ptok[b * plen + 1] = c.transcribe_token();
-      if (!m->ts) ptok[b * plen + 2] = c.no_timestamps_token();
+      if (!call.ts) ptok[b * plen + 2] = c.no_timestamps_token();
     }
     WA_HIP(hipMemcpyAsync(g.prompt_tok, ptok.data(), (size_t)B * plen * 4, hipMemcpyHostToDevice, st));
     // SOT rows: embed reads tokens[b * Tq + t] with Tq = 1 -> a contiguous [B]
     // array: next_tok as scratch
     std::vector<int> sot(B, kSOT);
     WA_HIP(hipMemcpyAsync(g.next_tok, sot.data(), (size_t)B * 4, hipMemcpyHostToDevice, st));
-    WA_TRY(decoder_forward(m, g, g.next_tok, 1, nullptr, 0, 0, st));
+    WA_TRY(decoder_forward(m, g, call, g.next_tok, 1, nullptr, 0, 0, st));
     WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 50259, 50259 + c.n_lang, 0, g.prompt_tok, plen, m->range_flag, st));
-    if (m->score) WA_TRY(score_sot(m, g, g.logits, g.prompt_tok, plen, 0, st));  // before the next pass rewrites g.logits
+    if (call.score) WA_TRY(score_sot(m, g, g.logits, g.prompt_tok, plen, 0, st));  // before the next pass rewrites g.logits
     // ... then forward_prompt([lang, TRANSCRIBE, NO_TIMESTAMPS]) OVERWRITES the
     // cache from index 0 with positions 0..2 (decoder.rs:272-283) while the
     // position counter continues at 1 + 3 = 4 (whisper.rs:74,93) -- without
     // NO_TIMESTAMPS: positions 0..1, the counter at 1 + 2.
-    WA_TRY(decoder_forward(m, g, g.prompt_tok, plen, nullptr, 0, 0, st));
+    WA_TRY(decoder_forward(m, g, call, g.prompt_tok, plen, nullptr, 0, 0, st));
     pos0 = 1 + plen;
     kv0 = plen;
   }
-  if (m->sample) {
+  if (call.sample) {
     // the clips' temperatures and seeds (pageable: the copies are staged before the calls return)
-    WA_HIP(hipMemcpyAsync(g.smp_temp, m->smp_temp + g.clip0, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    WA_HIP(hipMemcpyAsync(g.smp_seed, m->smp_seed + g.clip0, (size_t)B * 8, hipMemcpyHostToDevice, st));
+    WA_HIP(hipMemcpyAsync(g.smp_temp, call.temp + g.clip0, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    WA_HIP(hipMemcpyAsync(g.smp_seed, call.seed + g.clip0, (size_t)B * 8, hipMemcpyHostToDevice, st));
   }
-  if (m->ts) {  // every clip's rule record back to the empty history
-    const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, m->ts_max_initial));  // pageable: staged
+  if (call.ts) {  // every clip's rule record back to the empty history
+    const std::vector<TsRule> first(B, ts_rule_first(m->ts0(), c.n_vocab, call.ts_max_initial));  // pageable: staged
     WA_HIP(hipMemcpyAsync(g.ts_rules, first.data(), (size_t)B * sizeof(TsRule), hipMemcpyHostToDevice, st));
   }
-  if (m->sample || m->ts) {
+  if (call.sample || call.ts) {
     // pick 0 and its log-probability through the row kernel: under the first
     // pick's rule record (rule e; EOT is masked with the text) or with EOT
     // suppressed (whisper.rs:97-99)
-    const PickArgs p = pick_args(m, g);
+    const PickArgs p = pick_args(m, g, call);
     WA_HIP(launch_row_pick(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, p.rules, p.ts0, p.temp, p.seed, 0,
                            g.next_tok, g.next_lp, nullptr, m->range_flag, st));
   } else {
     // first token: EOT suppressed (whisper.rs:97-99)
     WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, g.next_tok, 1, m->range_flag, st));
-    if (m->score)  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
+    if (call.score)  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
       WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st));
   }
-  if (m->score) WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
+  if (call.score) WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
   // frozen clips start done, and counted: the loop stops once the live ones emitted EOT
   std::vector<int> done0(B, 0);
   int n_frozen = 0;
-  if (m->frozen)
-    for (int b = 0; b < B; ++b) n_frozen += done0[b] = m->frozen[g.clip0 + b] ? 1 : 0;
+  if (call.frozen)
+    for (int b = 0; b < B; ++b) n_frozen += done0[b] = call.frozen[g.clip0 + b] ? 1 : 0;
   const DecodeState init{pos0 - 1, kv0 - 1, -1, n_frozen};
   WA_HIP(hipMemcpyAsync(g.state, &init, sizeof(init), hipMemcpyHostToDevice, st));
   WA_HIP(hipMemsetAsync(g.ntok, 0, (size_t)B * 4, st));
@@ -583,21 +584,13 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st
 }
 
 // Capture (once per group size / eot mode) the step graph of group g.
-wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
-  // everything the captured step bakes in: the clip range (self-KV and
-  // encoder-plane offsets), the EOT mode and the trace buffers, the range
-  // tier, the cross-attention's frame split (its splits fix the plan of a T)
-  // and the planes' cache residency (a group that decoded alone and then
-  // decodes in a pair recaptures); one explicit field per mixed-radix digit
-  const int64_t key =
-      ((((((((int64_t)g.lane * 512 + g.b0) * 512 + g.nb) * 2 + (eot_stop ? 1 : 0)) * 2 + (m->trace_out ? 1 : 0)) * 2 +
-         (m->group_kv(g) ? 1 : 0)) * 4 + m->range_tier) * 16 + g.xplan.splits) * (kXattnResDen + 1) + g.xres.q +
-      // scoring, the top digit (above every lane): an unscored key is what it was
-      (m->score ? (int64_t)kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0) +
-      // timestamps, the digit above it: the rule's max_initial is in the records, not in the graph
-      (m->ts ? (int64_t)2 * kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0) +
-      // sampling, the digit above that: temperatures and seeds are read from the group's arrays, not baked in
-      (m->sample ? (int64_t)4 * kMaxLanes * 512 * 512 * 2 * 2 * 2 * 4 * 16 * (kXattnResDen + 1) : 0);
+wq4_status ensure_graph(wa_model* m, DecGroup& g, const DecodeCall& call) {
+  // a group that decoded alone and then decodes in a pair, or in another mode, recaptures
+  const char* bad = nullptr;
+  const int64_t key = graph_key((call.score ? 1 : 0) + (call.ts ? 2 : 0) + (call.sample ? 4 : 0), g.lane, g.b0, g.nb,
+                                call.eot_stop ? 1 : 0, call.trace_out ? 1 : 0, m->group_kv(g) ? 1 : 0, m->range_tier,
+                                g.xplan.splits, g.xres.q, &bad);
+  if (key < 0) return fail(WQ4_EINVAL, std::string("step-graph key: digit '") + bad + "' is outside its radix");
   if (g.graph && g.graph_key == key) return WQ4_OK;
   // the other layouts' graphs are kept: a call goes from units of three to
   // pairs or a lone last batch, beside the masked stream and without it, and
@@ -625,7 +618,7 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop) {
   WA_WQ4(wq4_prepare_stream(m->device, g.st));  // split-K workspace exists before capture
   hipGraph_t gr;
   WA_HIP(hipStreamBeginCapture(g.st, hipStreamCaptureModeThreadLocal));
-  wq4_status s = decode_step(m, g, eot_stop, g.st);
+  wq4_status s = decode_step(m, g, call, g.st);
   hipError_t ce = hipStreamEndCapture(g.st, &gr);
   if (s != WQ4_OK) return s;
   if (ce != hipSuccess) return fail(WQ4_EHIP, std::string("graph capture: ") + hipGetErrorString(ce));
@@ -686,7 +679,7 @@ wq4_status ensure_ffn_ws(wa_model* m) {
 // The score buffers of every decode group (DecGroup::next_lp ..), each sized
 // for the whole batch like the group's other buffers: allocated by the first
 // scored transcribe, all or nothing, never released.
-wq4_status ensure_score_buffers(wa_model* m) {
+static wq4_status ensure_score_buffers(wa_model* m) {
   if (m->score_alloc_ok) return WQ4_OK;
   const size_t B = (size_t)m->bmax, V = (size_t)m->cfg.n_vocab;
   bool ok = true;
@@ -717,7 +710,7 @@ wq4_status ensure_score_buffers(wa_model* m) {
 
 // The timestamp buffers of every decode group (DecGroup::ts_rules ..):
 // allocated by the first timestamp transcribe, all or nothing, never released.
-wq4_status ensure_ts_buffers(wa_model* m) {
+static wq4_status ensure_ts_buffers(wa_model* m) {
   if (m->ts_alloc_ok) return WQ4_OK;
   const size_t B = (size_t)m->bmax;
   bool ok = true;
@@ -740,7 +733,7 @@ wq4_status ensure_ts_buffers(wa_model* m) {
 
 // The sampling buffers of every decode group (DecGroup::smp_temp ..):
 // allocated by the first sampled transcribe, all or nothing, never released.
-wq4_status ensure_sample_buffers(wa_model* m) {
+static wq4_status ensure_sample_buffers(wa_model* m) {
   if (m->sample_alloc_ok) return WQ4_OK;
   const size_t B = (size_t)m->bmax;
   bool ok = true;
@@ -760,6 +753,14 @@ wq4_status ensure_sample_buffers(wa_model* m) {
   }
   m->bytes += m->groups.size() * B * 12;
   m->sample_alloc_ok = true;
+  return WQ4_OK;
+}
+
+wq4_status prepare_call(wa_model* m, const DecodeCall& call) {
+  WA_HIP(hipSetDevice(m->device));
+  if (call.score) WA_TRY(ensure_score_buffers(m));
+  if (call.ts) WA_TRY(ensure_ts_buffers(m));
+  if (call.sample) WA_TRY(ensure_sample_buffers(m));
   return WQ4_OK;
 }
 

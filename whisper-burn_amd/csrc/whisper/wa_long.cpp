@@ -96,6 +96,8 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
   const int S = n_streams, T = o->max_tokens, n_mels = m->cfg.n_mels, ts0 = m->ts0();
   const size_t slots = (size_t)T + 1;
   const int bmax = std::min(m->bmax, S);
+  // every round's ladder: sampled, with timestamps, stopping at EOT
+  const DecodeCall call(o->lang_token, T, 1, true, true, o->max_initial, true);
   WA_HIP(hipSetDevice(m->device));
   Dev d;
   float* max_dev = d.alloc<float>(S);
@@ -120,9 +122,7 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
   fb.n_temperatures = o->n_temperatures;
   fb.logprob_threshold = o->logprob_threshold;
   fb.no_speech_threshold = o->no_speech_threshold;
-  fb.seed = c_seed.data();
-  fb.timestamps = 1;
-  fb.max_initial = o->max_initial;
+  fb.seed = c_seed.data();  // (timestamps and max_initial: the call's)
   std::vector<wa_segment> segs(T);
   float sums[5] = {0, 0, 0, 0, 0};
   for (;;) {
@@ -139,8 +139,8 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
     }
     WA_TRY(wa_long_mel_windows(m->device, audio_dev, B, c_off.data(), c_n.data(), c_seek.data(), c_max.data(),
                                max_dev, n_mels, mel_dev, stream));
-    WA_TRY(transcribe_ladder(m, mel_dev, B, o->lang_token, T, 1, &fb, tok.data(), nt.data(), &scores, rung.data(),
-                             stream));
+    WA_TRY(prepare_call(m, call));  // the first round allocates the mode's buffers
+    WA_TRY(transcribe_ladder(m, call, mel_dev, B, &fb, tok.data(), nt.data(), &scores, rung.data(), stream));
     for (int i = 0; i < 5; ++i) sums[i] += m->timings[i];
     for (int c = 0; c < B; ++c) {
       const int r = rec[c];

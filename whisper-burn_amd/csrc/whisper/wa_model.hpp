@@ -167,7 +167,7 @@ struct DecGroup {
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
-  int64_t graph_key = -1;  // (sampling, timestamps, scoring, lane, b0, nb, eot mode, trace, frame split, plane residency) the graph was captured for
+  int64_t graph_key = -1;  // wa::graph_key of the layout and mode the graph was captured for
   // graphs of other layouts this group ran (ensure_graph): a call of units of
   // three and two, with and without the masked stream beside them, goes
   // through four keys per group and comes back to each
@@ -178,6 +178,77 @@ struct DecGroup {
   KeptGraph kept[kKeptGraphs];
   int kept_next = 0;  // the slot the next parked graph replaces once all are taken
 };
+
+// One transcribe call's decode: built by its entry and passed down to every
+// prompt, step and pick of the call (the model holds no mode).
+struct DecodeCall {
+  int lang_token = -1, max_tokens = 0, eot_stop = 0;
+  // score: prompts and steps also leave the picks' log-probabilities, the
+  // no-speech and the language probability in the groups' score buffers.
+  // ts: the prompt drops NO_TIMESTAMPS and every pick runs under the timestamp
+  // rules, the first timestamp at most ts_max_initial ids past <|0.00|> (< 0:
+  // unbounded).  sample: every pick is the Gumbel-max pick at the clip's
+  // temperature and seed.  ts or sample imply score (the constructor sees to
+  // it): such a pick always leaves its log-probability.
+  bool score = false, ts = false, sample = false;
+  int ts_max_initial = 50;
+  // sampled calls: host arrays over the call's clips (DecGroup::clip0 indexes
+  // them), read by the prompts.  frozen (nullable): clips that start the decode
+  // done -- their picks go nowhere and the decode stops once the live clips
+  // emitted EOT (the fallback ladder's re-decodes).
+  const float* temp = nullptr;
+  const uint64_t* seed = nullptr;
+  const uint8_t* frozen = nullptr;
+  // decode-step logit trace (wa_transcribe_trace; null otherwise): device
+  // [clip][trace_s1][trace_k] ids and their logits
+  const int* trace_ids = nullptr;
+  float* trace_out = nullptr;
+  int trace_s1 = 0, trace_k = 0;
+
+  DecodeCall() = default;
+  DecodeCall(int lang, int max_tok, int eot, bool score_, bool ts_ = false, int max_initial = 50, bool sample_ = false)
+      : lang_token(lang), max_tokens(max_tok), eot_stop(eot), score(score_ || ts_ || sample_), ts(ts_), sample(sample_),
+        ts_max_initial(max_initial) {}
+  // the same call over other per-clip arrays (a rung of the fallback ladder)
+  DecodeCall with_clips(const float* t, const uint64_t* s, const uint8_t* f) const {
+    DecodeCall c = *this;
+    c.temp = t;
+    c.seed = s;
+    c.frozen = f;
+    return c;
+  }
+  // the call whose clip 0 is this call's clip c (one batch of a call over several)
+  DecodeCall at_clip(size_t c) const {
+    return with_clips(temp ? temp + c : nullptr, seed ? seed + c : nullptr, frozen ? frozen + c : nullptr);
+  }
+};
+
+// Everything a captured decode step bakes in, as one mixed-radix number, most
+// significant digit first: the mode (score = 1, ts = 2, sample = 4; the rule's
+// max_initial, the temperatures and the seeds are read at run time), the clip
+// range (self-KV and encoder-plane offsets), the EOT mode, the trace buffers,
+// the few-clip caches, the range tier, the cross-attention's frame split (its
+// splits fix the plan of a T) and the planes' cache residency.  A digit
+// outside its radix would alias another layout's key: -1, *bad naming it.
+inline int64_t graph_key(int mode, int lane, int b0, int nb, int eot, int trace, int group_kv, int range_tier,
+                         int splits, int q, const char** bad = nullptr) {
+  const struct {
+    const char* name;
+    int value, radix;
+  } digits[] = {{"mode", mode, 8},         {"lane", lane, kMaxLanes},     {"b0", b0, 512},
+                {"nb", nb, 512},           {"eot", eot, 2},               {"trace", trace, 2},
+                {"group_kv", group_kv, 2}, {"range_tier", range_tier, 4}, {"splits", splits, 16},
+                {"residency", q, kXattnResDen + 1}};
+  int64_t key = 0;
+  for (const auto& d : digits) {
+    if (d.value < 0 || d.value >= d.radix) {
+      if (bad) *bad = d.name;
+      return -1;
+    }
+    key = key * d.radix + d.value;
+  }
+  return key;
+}
 
 }  // namespace wa
 
@@ -258,38 +329,10 @@ struct wa_model {
   void* ffn_ws = nullptr;
   size_t ffn_ws_bytes = 0;
   float timings[5] = {0, 0, 0, 0, 0};
-  // decode-step logit trace (wa_transcribe_trace; null otherwise): device
-  // [clip][trace_s1][trace_k] ids and their logits
-  const int* trace_ids = nullptr;
-  float* trace_out = nullptr;
-  int trace_s1 = 0, trace_k = 0;
-  // a scored transcribe is running (wa_transcribe_scored /
-  // wa_transcribe_batches_scored; false otherwise): prompts and steps also
-  // leave the picks' log-probabilities, the no-speech and the language
-  // probability in the groups' score buffers
-  bool score = false;
-  bool score_alloc_ok = false;  // every group's score buffers allocated (ensure_score_buffers)
-  // a timestamp transcribe is running (wa_transcribe_timestamps /
-  // wa_transcribe_batches_timestamps; `score` is set with it): the prompt
-  // drops NO_TIMESTAMPS and every pick runs under the timestamp rules, the
-  // first timestamp at most ts_max_initial ids past <|0.00|> (< 0: unbounded)
-  bool ts = false;
-  int ts_max_initial = 50;
-  bool ts_alloc_ok = false;  // every group's timestamp buffers allocated (ensure_ts_buffers)
+  // every group's score / timestamp / sampling buffers are allocated
+  // (prepare_call: by the first call in that mode, all or nothing)
+  bool score_alloc_ok = false, ts_alloc_ok = false, sample_alloc_ok = false;
   int ts0() const { return cfg.no_timestamps_token() + 1; }  // <|0.00|>
-  // a sampled transcribe is running (wa_transcribe_sampled /
-  // wa_transcribe_batches_sampled / wa_transcribe_fallback; `score` is set
-  // with it, `ts` when it decodes timestamps): every pick is the Gumbel-max
-  // pick at the clip's temperature and seed -- host arrays over the call's
-  // clips, read by the prompts.  frozen (nullable, host, per clip of the
-  // batch): clips that start the decode done -- their picks go nowhere and
-  // the decode stops once the live clips emitted EOT (the fallback ladder's
-  // re-decodes).
-  bool sample = false;
-  const float* smp_temp = nullptr;
-  const uint64_t* smp_seed = nullptr;
-  const uint8_t* frozen = nullptr;
-  bool sample_alloc_ok = false;  // every group's sampling buffers allocated (ensure_sample_buffers)
   // live kernel timing (wa_profile_*)
   struct Pending {
     hipEvent_t a, b;
@@ -360,9 +403,7 @@ wq4_status build_ln_fold(wa_model* m);
 void kv_config(wa_model* m, int max_batch);
 wq4_status alloc_activations(wa_model* m);
 wq4_status ensure_ffn_ws(wa_model* m);
-wq4_status ensure_score_buffers(wa_model* m);
-wq4_status ensure_ts_buffers(wa_model* m);
-wq4_status ensure_sample_buffers(wa_model* m);
+wq4_status prepare_call(wa_model* m, const DecodeCall& call);  // the device, and the buffers the call's mode needs
 int decode_groups(int B);
 wq4_status encoder_front(wa_model* m, const float* mel, int B, hipStream_t st);
 wq4_status encoder_layers(wa_model* m, int B, int l0, int l1, hipStream_t st);
@@ -370,16 +411,17 @@ wq4_status encoder_post(wa_model* m, int B, hipStream_t st, float* enc_out_f32);
 wq4_status encoder_forward(wa_model* m, const float* mel, int B, hipStream_t st, float* enc_out_f32);
 wq4_status cross_kv_forward(wa_model* m, int B, hipStream_t st, bool caches, int lane = 0);
 int ensure_lanes(wa_model* m, int want);
-wq4_status decoder_forward(wa_model* m, DecGroup& g, const int* tokens, int Tq, const DecodeState* state, int pos0,
-                           int kv0, hipStream_t st);
-wq4_status prompt_group(wa_model* m, DecGroup& g, int lang_token, hipStream_t st);
-wq4_status ensure_graph(wa_model* m, DecGroup& g, int eot_stop);
+wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, const int* tokens, int Tq,
+                           const DecodeState* state, int pos0, int kv0, hipStream_t st);
+wq4_status prompt_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st);
+wq4_status ensure_graph(wa_model* m, DecGroup& g, const DecodeCall& call);
 
 // ---- wa_transcribe.cpp
 bool bad_temperatures(const float* t, int n);  // one is negative or not finite
-// The ladder of wa_transcribe_fallback on checked arguments (wa_long.cpp runs it per round).
-wq4_status transcribe_ladder(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                             int eot_stop, const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
+// The ladder of wa_transcribe_fallback on checked arguments and a prepared
+// sampled call (wa_long.cpp runs it per round).
+wq4_status transcribe_ladder(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
+                             const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
                              const wa_scores* scores, int32_t* rung_out, void* stream);
 
 }  // namespace wa

@@ -119,9 +119,9 @@ int unit_groups(int B, int n) { return n > 1 ? n : decode_groups(B); }
 // budget at three lanes: DESIGN.md section 10).
 // batch0: the index, among the call's batches, of the batch in lane 0 -- where
 // the groups' clips sit in the call's per-clip host arrays (DecGroup::clip0).
-wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token, int max_tokens, int eot_stop,
-                      hipEvent_t ready, const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps,
-                      int batch0 = 0) {
+wq4_status run_decode(wa_model* m, const DecodeCall& call, int B, int n, int masked_cus, hipEvent_t ready,
+                      const hipEvent_t* gprompt, const hipEvent_t* gdone, int* gsteps, int batch0 = 0) {
+  const int eot_stop = call.eot_stop;
   const int G = unit_groups(B, n);
   // the groups decode concurrently: the planes of all their clips are live
   // (every lane of a unit), which decides the share each keeps cached
@@ -142,9 +142,9 @@ wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token,
     g.nb = n > 1 ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
     g.clip0 = (batch0 + g.lane) * B + g.b0;
     WA_HIP(hipStreamWaitEvent(g.st, ready, 0));
-    WA_TRY(prompt_group(m, g, lang_token, g.st));
+    WA_TRY(prompt_group(m, g, call, g.st));
     WA_HIP(hipEventRecord(gprompt[i], g.st));
-    WA_TRY(ensure_graph(m, g, eot_stop));
+    WA_TRY(ensure_graph(m, g, call));
   }
   // greedy loop (whisper.rs:104-125): each step replays every live group's
   // graph; a group stops once all its clips emitted EOT (polled with a lag)
@@ -160,7 +160,7 @@ wq4_status run_decode(wa_model* m, int B, int n, int masked_cus, int lang_token,
     live[i] = true;
     gsteps[i] = 0;
   }
-  for (int step = 0; step < max_tokens && nlive > 0; ++step) {
+  for (int step = 0; step < call.max_tokens && nlive > 0; ++step) {
     for (int i = 0; i < G; ++i) {
       if (!live[i]) continue;
       DecGroup& g = m->groups[i];
@@ -249,17 +249,17 @@ void copy_scores(const float* sc, int B, int max_tokens, const wa_scores* out, s
 }
 
 // One transcribe (whisper.rs:51-128 for a batch of clips); *overflow = the
-// range flag of this run (see wa_model::range_flag).  scores (a scored
-// transcribe, m->score; null otherwise): this run's scores too.
+// range flag of this run (see wa_model::range_flag).  scores (a scored call;
+// null otherwise): this run's scores too.
 // reuse_enc (the fallback ladder's re-decodes): no encoder pass -- the prompt
 // and the loop run again over the planes (and few-clip caches) the last pass
 // left, and the prompt / decode times and steps are added to the timings.
-wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                           int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, bool* overflow,
-                           const wa_scores* scores, bool reuse_enc = false) {
+wq4_status transcribe_once(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips, int32_t* tokens_out,
+                           int32_t* n_tokens_out, void* stream, bool* overflow, const wa_scores* scores,
+                           bool reuse_enc = false) {
   // all work on the model's own stream, ordered after the caller's stream
   hipStream_t st = m->own_stream;
-  const int B = n_clips;
+  const int B = n_clips, max_tokens = call.max_tokens;
   const int G = decode_groups(B);
   EventSet ev;
   hipEvent_t e_in, e_enc, e_kv, e_ready, e_end, gprompt[kMaxGroups], gdone[kMaxGroups];
@@ -280,7 +280,7 @@ wq4_status transcribe_once(wa_model* m, const float* mel_dev, int n_clips, int l
   // decode groups: contiguous clip ranges on their own streams, started
   // after the encoder-planes pass, joined back into `st` at the end
   int gsteps[kMaxGroups] = {};
-  WA_TRY(run_decode(m, B, 1, 0, lang_token, max_tokens, eot_stop, e_ready, gprompt, gdone, gsteps));
+  WA_TRY(run_decode(m, call, B, 1, 0, e_ready, gprompt, gdone, gsteps));
   const int steps = *std::max_element(gsteps, gsteps + G);  // the last group to stop
   std::vector<int32_t> tok((size_t)B * kMaxTokens), nt(B);
   int flag = 0;
@@ -373,9 +373,10 @@ wq4_status ensure_enc_stream(wa_model* m) {
 // as for a pair, to the CUs the masked stream and the peer groups leave.  A
 // call is cut into units by unit_sizes: widest first, and two units of two
 // in place of a unit of three and a lone batch.  One more group stream.
-wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B, int lang_token, int max_tokens,
-                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags,
+wq4_status transcribe_pipelined(wa_model* m, const DecodeCall& call, const float* mel_dev, int NB, int B,
+                                int32_t* tokens_out, int32_t* n_tokens_out, void* stream, int* flags,
                                 const wa_scores* scores) {
+  const int max_tokens = call.max_tokens, eot_stop = call.eot_stop;
   WA_TRY(ensure_enc_stream(m));
   hipStream_t st = m->own_stream, es = m->enc_stream;
   const int L = (int)m->enc.size();
@@ -498,8 +499,7 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
       WA_HIP(hipEventRecord(u.mend, es));
     }
     // the masked part above takes its CUs from this decode; the last unit has them all
-    WA_TRY(run_decode(m, B, u.n, i + 1 < NU ? m->enc_cus : 0, lang_token, max_tokens, eot_stop, u.ready, u.gprompt,
-                      u.gdone, u.gsteps, u.first));
+    WA_TRY(run_decode(m, call, B, u.n, i + 1 < NU ? m->enc_cus : 0, u.ready, u.gprompt, u.gdone, u.gsteps, u.first));
     int32_t* hb = host + (size_t)u.first * per;
     WA_TRY(collect_batch(m, B, u.n, u.gdone, st, hb, hb + (size_t)B * kMaxTokens, hb + (size_t)B * kMaxTokens + B,
                          per, scores ? reinterpret_cast<float*>(hb + per0) : nullptr));
@@ -568,44 +568,6 @@ wq4_status transcribe_pipelined(wa_model* m, const float* mel_dev, int NB, int B
 
 }  // namespace
 
-// The timestamp mode around a transcribe: the score and timestamp buffers,
-// then m->ts (and m->score: a timestamp pick always leaves its
-// log-probability) for the length of `run`.
-template <class Run>
-static wq4_status with_timestamps(wa_model* m, int max_initial, Run run) {
-  WA_HIP(hipSetDevice(m->device));
-  WA_TRY(ensure_score_buffers(m));
-  WA_TRY(ensure_ts_buffers(m));
-  m->score = m->ts = true;
-  m->ts_max_initial = max_initial;
-  const wq4_status s = run();
-  m->score = m->ts = false;
-  return s;
-}
-
-// The sampling mode around a transcribe: the score, sampling and (timestamps)
-// rule buffers, then m->sample with m->score (and m->ts) and the call's
-// per-clip temperatures and seeds for the length of `run`.
-template <class Run>
-static wq4_status with_sampling(wa_model* m, const float* temp, const uint64_t* seed, int timestamps, int max_initial,
-                                Run run) {
-  WA_HIP(hipSetDevice(m->device));
-  WA_TRY(ensure_score_buffers(m));
-  if (timestamps) WA_TRY(ensure_ts_buffers(m));
-  WA_TRY(ensure_sample_buffers(m));
-  m->score = m->sample = true;
-  m->ts = timestamps != 0;
-  if (timestamps) m->ts_max_initial = max_initial;
-  m->smp_temp = temp;
-  m->smp_seed = seed;
-  const wq4_status s = run();
-  m->score = m->sample = m->ts = false;
-  m->smp_temp = nullptr;
-  m->smp_seed = nullptr;
-  m->frozen = nullptr;
-  return s;
-}
-
 bool wa::bad_temperatures(const float* t, int n) {
   for (int i = 0; i < n; ++i)
     if (!(t[i] >= 0.0f) || !std::isfinite(t[i])) return true;
@@ -627,75 +589,69 @@ static wq4_status raise_tier(wa_model* m) {
 // wa_transcribe_long), its arguments checked by the entry: one encoder pass,
 // then per rung a prompt + decode over the same planes with the clips that
 // have passed frozen.
-wq4_status wa::transcribe_ladder(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                                 int eot_stop, const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
+wq4_status wa::transcribe_ladder(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
+                                 const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
                                  const wa_scores* scores, int32_t* rung_out, void* stream) {
-  const int B = n_clips, R = fb->n_temperatures;
+  const int B = n_clips, R = fb->n_temperatures, max_tokens = call.max_tokens;
   const size_t slots = (size_t)max_tokens + 1;
   std::vector<float> temp(B);
   std::vector<uint64_t> seed(B);
-  return with_sampling(m, temp.data(), seed.data(), fb->timestamps, fb->max_initial, [&]() -> wq4_status {
-    // one rung's results; the clips it was run for are copied to the caller's arrays
-    std::vector<int32_t> tok((size_t)B * max_tokens), nt(B), lt(B);
-    std::vector<float> lp((size_t)B * slots), ns(B), lpr(B);
-    const wa_scores rung_scores{lp.data(), ns.data(), lt.data(), lpr.data()};
-    for (;;) {  // the range tiers: a flagged rung restarts the ladder one tier up
-      bool overflow = false;
-      std::vector<uint8_t> frozen(B, 0);
-      int n_frozen = 0;
-      for (int r = 0; r < R && n_frozen < B && !overflow; ++r) {
-        for (int c = 0; c < B; ++c) {
-          temp[c] = fb->temperatures[r];
-          seed[c] = fb->seed[c] + (uint64_t)r;
+  // one rung's results; the clips it was run for are copied to the caller's arrays
+  std::vector<int32_t> tok((size_t)B * max_tokens), nt(B), lt(B);
+  std::vector<float> lp((size_t)B * slots), ns(B), lpr(B);
+  const wa_scores rung_scores{lp.data(), ns.data(), lt.data(), lpr.data()};
+  for (;;) {  // the range tiers: a flagged rung restarts the ladder one tier up
+    bool overflow = false;
+    std::vector<uint8_t> frozen(B, 0);
+    int n_frozen = 0;
+    for (int r = 0; r < R && n_frozen < B && !overflow; ++r) {
+      for (int c = 0; c < B; ++c) {
+        temp[c] = fb->temperatures[r];
+        seed[c] = fb->seed[c] + (uint64_t)r;
+      }
+      const DecodeCall rung = call.with_clips(temp.data(), seed.data(), r > 0 ? frozen.data() : nullptr);
+      WA_TRY(transcribe_once(m, rung, mel_dev, B, tok.data(), nt.data(), stream, &overflow, &rung_scores, r > 0));
+      if (overflow) break;
+      for (int c = 0; c < B; ++c) {
+        if (frozen[c]) continue;
+        std::memcpy(tokens_out + (size_t)c * max_tokens, tok.data() + (size_t)c * max_tokens, (size_t)max_tokens * 4);
+        n_tokens_out[c] = nt[c];
+        if (rung_out) rung_out[c] = r;
+        if (scores) {
+          if (scores->token_logprob) std::memcpy(scores->token_logprob + c * slots, lp.data() + c * slots, slots * 4);
+          if (scores->no_speech_prob) scores->no_speech_prob[c] = ns[c];
+          if (scores->lang_token) scores->lang_token[c] = lt[c];
+          if (scores->lang_prob) scores->lang_prob[c] = lpr[c];
         }
-        m->frozen = r > 0 ? frozen.data() : nullptr;
-        WA_TRY(transcribe_once(m, mel_dev, B, lang_token, max_tokens, eot_stop, tok.data(), nt.data(), stream,
-                               &overflow, &rung_scores, r > 0));
-        if (overflow) break;
-        for (int c = 0; c < B; ++c) {
-          if (frozen[c]) continue;
-          std::memcpy(tokens_out + (size_t)c * max_tokens, tok.data() + (size_t)c * max_tokens, (size_t)max_tokens * 4);
-          n_tokens_out[c] = nt[c];
-          if (rung_out) rung_out[c] = r;
-          if (scores) {
-            if (scores->token_logprob)
-              std::memcpy(scores->token_logprob + c * slots, lp.data() + c * slots, slots * 4);
-            if (scores->no_speech_prob) scores->no_speech_prob[c] = ns[c];
-            if (scores->lang_token) scores->lang_token[c] = lt[c];
-            if (scores->lang_prob) scores->lang_prob[c] = lpr[c];
+        // the ladder rule: the mean of the stored log-probabilities below the
+        // threshold, unless the no-speech score calls the clip silence
+        // (comparisons with a NaN threshold are false: that test is off)
+        double sum = 0.0;
+        int cnt = 0;
+        for (size_t i = 0; i < slots; ++i) {
+          const float v = lp[c * slots + i];
+          if (!std::isnan(v)) {
+            sum += v;
+            ++cnt;
           }
-          // the ladder rule: the mean of the stored log-probabilities below the
-          // threshold, unless the no-speech score calls the clip silence
-          // (comparisons with a NaN threshold are false: that test is off)
-          double sum = 0.0;
-          int cnt = 0;
-          for (size_t i = 0; i < slots; ++i) {
-            const float v = lp[c * slots + i];
-            if (!std::isnan(v)) {
-              sum += v;
-              ++cnt;
-            }
-          }
-          const double mean = cnt ? sum / cnt : 0.0;
-          const bool needs = mean < (double)fb->logprob_threshold && !(ns[c] > fb->no_speech_threshold);
-          if (!needs) {
-            frozen[c] = 1;
-            ++n_frozen;
-          }
+        }
+        const double mean = cnt ? sum / cnt : 0.0;
+        const bool needs = mean < (double)fb->logprob_threshold && !(ns[c] > fb->no_speech_threshold);
+        if (!needs) {
+          frozen[c] = 1;
+          ++n_frozen;
         }
       }
-      if (!overflow) return WQ4_OK;
-      WA_TRY(raise_tier(m));
     }
-  });
+    if (!overflow) return WQ4_OK;
+    WA_TRY(raise_tier(m));
+  }
 }
 
-extern "C" {
-
-// wa_transcribe, and wa_transcribe_scored with its scores: the scores are
-// those of the run whose tokens are returned.
-static wq4_status transcribe_tiers(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                                   int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream,
+// A transcribe through the range tiers; the scores are those of the run whose
+// tokens are returned.
+static wq4_status transcribe_tiers(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
+                                   int32_t* tokens_out, int32_t* n_tokens_out, void* stream,
                                    const wa_scores* scores) {
   // A flagged run is retried one range tier up (wa_model::range_tier), sticky
   // for the model: its activations evidently exceed the range below.
@@ -705,45 +661,20 @@ static wq4_status transcribe_tiers(wa_model* m, const float* mel_dev, int n_clip
   //           (tier 3 needs tier 2's workspaces, already allocated)
   for (;;) {
     bool overflow = false;
-    WA_TRY(transcribe_once(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
-                           &overflow, scores));
+    WA_TRY(transcribe_once(m, call, mel_dev, n_clips, tokens_out, n_tokens_out, stream, &overflow, scores));
     if (!overflow) return WQ4_OK;
     WA_TRY(raise_tier(m));
   }
 }
 
-wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                         int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  WA_HIP(hipSetDevice(m->device));
-  return transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
-                          nullptr);
-}
-
-wq4_status wa_transcribe_scored(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
-                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
-                                void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !scores) return fail(WQ4_EINVAL, "null argument");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  WA_HIP(hipSetDevice(m->device));
-  WA_TRY(ensure_score_buffers(m));
-  m->score = true;
-  const wq4_status s = transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                                        n_tokens_out, stream, scores);
-  m->score = false;
-  return s;
-}
-
-// wa_transcribe_batches, and wa_transcribe_batches_scored (m->score set) with its scores.
-static wq4_status transcribe_batches(wa_model* m, const float* mel_dev, int n_batches, int n_clips, int lang_token,
-                                     int max_tokens, int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out,
-                                     void* stream, const wa_scores* scores) {
+// The pipelined batches of a call, then the flagged ones through the tiers.
+static wq4_status transcribe_batches(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_batches,
+                                     int n_clips, int32_t* tokens_out, int32_t* n_tokens_out, void* stream,
+                                     const wa_scores* scores) {
+  const int max_tokens = call.max_tokens;
   std::vector<int> flags(n_batches, 0);
-  WA_TRY(transcribe_pipelined(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                              n_tokens_out, stream, flags.data(), scores));
+  WA_TRY(transcribe_pipelined(m, call, mel_dev, n_batches, n_clips, tokens_out, n_tokens_out, stream, flags.data(),
+                              scores));
   const size_t mel_stride = (size_t)n_clips * m->cfg.n_mels * 2 * m->cfg.n_audio_ctx;
   // the pipeline decoded every batch at the tier the model had on entry
   const int tier0 = m->range_tier;
@@ -752,116 +683,119 @@ static wq4_status transcribe_batches(wa_model* m, const float* mel_dev, int n_ba
     // once that raised the (sticky) tier, the later batches are re-run at it
     // too -- one wa_transcribe per batch would have decoded them there
     if (!flags[i] && m->range_tier == tier0) continue;
+    const size_t c0 = (size_t)i * n_clips;
     wa_scores at{};  // batch i's part of the caller's arrays
     if (scores) {
-      const size_t c0 = (size_t)i * n_clips;
       at.token_logprob = scores->token_logprob ? scores->token_logprob + c0 * (max_tokens + 1) : nullptr;
       at.no_speech_prob = scores->no_speech_prob ? scores->no_speech_prob + c0 : nullptr;
       at.lang_token = scores->lang_token ? scores->lang_token + c0 : nullptr;
       at.lang_prob = scores->lang_prob ? scores->lang_prob + c0 : nullptr;
     }
-    // a sampled call: batch i's temperatures and seeds lead the per-clip arrays for the re-run
-    const float* const temp = m->smp_temp;
-    const uint64_t* const seed = m->smp_seed;
-    if (m->sample) {
-      m->smp_temp = temp + (size_t)i * n_clips;
-      m->smp_seed = seed + (size_t)i * n_clips;
-    }
-    const wq4_status rs =
-        transcribe_tiers(m, mel_dev + i * mel_stride, n_clips, lang_token, max_tokens, eot_stop,
-                         tokens_out + (size_t)i * n_clips * max_tokens, n_tokens_out + (size_t)i * n_clips, stream,
-                         scores ? &at : nullptr);
-    m->smp_temp = temp;
-    m->smp_seed = seed;
-    WA_TRY(rs);
+    // (a sampled call: batch i's temperatures and seeds lead the re-run's per-clip arrays)
+    WA_TRY(transcribe_tiers(m, call.at_clip(c0), mel_dev + i * mel_stride, n_clips, tokens_out + c0 * max_tokens,
+                            n_tokens_out + c0, stream, scores ? &at : nullptr));
   }
   return WQ4_OK;
+}
+
+// The transcribe entries' argument check, in one order.  ptrs_ok: no pointer
+// the entry needs is null.  temps (nullable): a ladder's temperatures, one per
+// rung (`rungs` set), or a sampled call's, one per clip.
+static wq4_status check_args(const wa_model* m, bool ptrs_ok, int n_batches, int max_tokens, int n_clips,
+                             const float* temps = nullptr, const int* rungs = nullptr) {
+  if (!m || !ptrs_ok) return fail(WQ4_EINVAL, "null argument");
+  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
+  if (rungs && (*rungs < 1 || *rungs > 8)) return fail(WQ4_EINVAL, "the ladder has 1 .. 8 rungs");
+  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
+  if (temps && bad_temperatures(temps, rungs ? *rungs : n_clips >= 1 ? n_batches * n_clips : 0))
+    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");  // last: the only read of *m
+  return WQ4_OK;
+}
+
+static DecodeCall sampled_call(int lang_token, int max_tokens, int eot_stop, const wa_sampling& s) {
+  return DecodeCall(lang_token, max_tokens, eot_stop, true, s.timestamps != 0, s.max_initial, true)
+      .with_clips(s.temperature, s.seed, nullptr);
+}
+
+extern "C" {
+
+// Every entry: build the call, check the arguments, prepare the model, run.
+
+wq4_status wa_transcribe(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                         int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, void* stream) {
+  const DecodeCall call(lang_token, max_tokens, eot_stop, false);
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out, 1, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  return transcribe_tiers(m, call, mel_dev, n_clips, tokens_out, n_tokens_out, stream, nullptr);
+}
+
+wq4_status wa_transcribe_scored(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
+                                void* stream) {
+  const DecodeCall call(lang_token, max_tokens, eot_stop, true);
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out && scores, 1, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  return transcribe_tiers(m, call, mel_dev, n_clips, tokens_out, n_tokens_out, stream, scores);
 }
 
 wq4_status wa_transcribe_batches(wa_model* m, const float* mel_dev, int n_batches, int n_clips, int lang_token,
                                  int max_tokens, int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out,
                                  void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
-  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  WA_HIP(hipSetDevice(m->device));
-  return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                            n_tokens_out, stream, nullptr);
+  const DecodeCall call(lang_token, max_tokens, eot_stop, false);
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out, n_batches, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  return transcribe_batches(m, call, mel_dev, n_batches, n_clips, tokens_out, n_tokens_out, stream, nullptr);
 }
 
 wq4_status wa_transcribe_batches_scored(wa_model* m, const float* mel_dev, int n_batches, int n_clips,
                                         int lang_token, int max_tokens, int eot_stop, int32_t* tokens_out,
                                         int32_t* n_tokens_out, const wa_scores* scores, void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !scores) return fail(WQ4_EINVAL, "null argument");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  WA_HIP(hipSetDevice(m->device));
-  WA_TRY(ensure_score_buffers(m));
-  m->score = true;
-  const wq4_status s = transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop,
-                                          tokens_out, n_tokens_out, stream, scores);
-  m->score = false;
-  return s;
+  const DecodeCall call(lang_token, max_tokens, eot_stop, true);
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out && scores, n_batches, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  return transcribe_batches(m, call, mel_dev, n_batches, n_clips, tokens_out, n_tokens_out, stream, scores);
 }
 
 wq4_status wa_transcribe_timestamps(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                                     int eot_stop, int max_initial, int32_t* tokens_out, int32_t* n_tokens_out,
                                     const wa_scores* scores, void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  return with_timestamps(m, max_initial, [&] {
-    return transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
-                            scores);
-  });
+  const DecodeCall call(lang_token, max_tokens, eot_stop, true, true, max_initial);
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out, 1, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  return transcribe_tiers(m, call, mel_dev, n_clips, tokens_out, n_tokens_out, stream, scores);
 }
 
 wq4_status wa_transcribe_batches_timestamps(wa_model* m, const float* mel_dev, int n_batches, int n_clips,
                                             int lang_token, int max_tokens, int eot_stop, int max_initial,
                                             int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
                                             void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out) return fail(WQ4_EINVAL, "null argument");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  return with_timestamps(m, max_initial, [&] {
-    return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                              n_tokens_out, stream, scores);
-  });
+  const DecodeCall call(lang_token, max_tokens, eot_stop, true, true, max_initial);
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out, n_batches, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  return transcribe_batches(m, call, mel_dev, n_batches, n_clips, tokens_out, n_tokens_out, stream, scores);
 }
 
+// (the sampled entries and the ladder read their struct to build the call: they check first)
 wq4_status wa_transcribe_sampled(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                                  int eot_stop, const wa_sampling* sampling, int32_t* tokens_out,
                                  int32_t* n_tokens_out, const wa_scores* scores, void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !sampling || !sampling->temperature || !sampling->seed)
-    return fail(WQ4_EINVAL, "null argument");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (n_clips >= 1 && bad_temperatures(sampling->temperature, n_clips))
-    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  return with_sampling(m, sampling->temperature, sampling->seed, sampling->timestamps, sampling->max_initial, [&] {
-    return transcribe_tiers(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out, n_tokens_out, stream,
-                            scores);
-  });
+  const bool ok = mel_dev && tokens_out && n_tokens_out && sampling && sampling->temperature && sampling->seed;
+  WA_TRY(check_args(m, ok, 1, max_tokens, n_clips, ok ? sampling->temperature : nullptr));
+  const DecodeCall call = sampled_call(lang_token, max_tokens, eot_stop, *sampling);
+  WA_TRY(prepare_call(m, call));
+  return transcribe_tiers(m, call, mel_dev, n_clips, tokens_out, n_tokens_out, stream, scores);
 }
 
 wq4_status wa_transcribe_batches_sampled(wa_model* m, const float* mel_dev, int n_batches, int n_clips,
                                          int lang_token, int max_tokens, int eot_stop, const wa_sampling* sampling,
                                          int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
                                          void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !sampling || !sampling->temperature || !sampling->seed)
-    return fail(WQ4_EINVAL, "null argument");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
-  if (n_clips >= 1 && bad_temperatures(sampling->temperature, n_batches * n_clips))
-    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  return with_sampling(m, sampling->temperature, sampling->seed, sampling->timestamps, sampling->max_initial, [&] {
-    return transcribe_batches(m, mel_dev, n_batches, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                              n_tokens_out, stream, scores);
-  });
+  const bool ok = mel_dev && tokens_out && n_tokens_out && sampling && sampling->temperature && sampling->seed;
+  WA_TRY(check_args(m, ok, n_batches, max_tokens, n_clips, ok ? sampling->temperature : nullptr));
+  const DecodeCall call = sampled_call(lang_token, max_tokens, eot_stop, *sampling);
+  WA_TRY(prepare_call(m, call));
+  return transcribe_batches(m, call, mel_dev, n_batches, n_clips, tokens_out, n_tokens_out, stream, scores);
 }
 
 // The temperature fallback ladder: one encoder pass, then per rung a prompt +
@@ -869,15 +803,11 @@ wq4_status wa_transcribe_batches_sampled(wa_model* m, const float* mel_dev, int 
 wq4_status wa_transcribe_fallback(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                                   int eot_stop, const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
                                   const wa_scores* scores, int32_t* rung_out, void* stream) {
-  if (!m || !mel_dev || !tokens_out || !n_tokens_out || !fb || !fb->temperatures || !fb->seed)
-    return fail(WQ4_EINVAL, "null argument");
-  if (fb->n_temperatures < 1 || fb->n_temperatures > 8) return fail(WQ4_EINVAL, "the ladder has 1 .. 8 rungs");
-  if (max_tokens < 1 || max_tokens > kMaxTokens) return fail(WQ4_EINVAL, "max_tokens must be in [1, 224]");
-  if (bad_temperatures(fb->temperatures, fb->n_temperatures))
-    return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
-  if (n_clips < 1 || n_clips > m->bmax) return fail(WQ4_EINVAL, "n_clips out of range");
-  return transcribe_ladder(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, fb, tokens_out, n_tokens_out, scores,
-                           rung_out, stream);
+  const bool ok = mel_dev && tokens_out && n_tokens_out && fb && fb->temperatures && fb->seed;
+  WA_TRY(check_args(m, ok, 1, max_tokens, n_clips, ok ? fb->temperatures : nullptr, ok ? &fb->n_temperatures : nullptr));
+  const DecodeCall call(lang_token, max_tokens, eot_stop, true, fb->timestamps != 0, fb->max_initial, true);
+  WA_TRY(prepare_call(m, call));
+  return transcribe_ladder(m, call, mel_dev, n_clips, fb, tokens_out, n_tokens_out, scores, rung_out, stream);
 }
 
 wq4_status wa_sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out) {
@@ -949,15 +879,14 @@ wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, i
                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const int32_t* trace_ids_dev,
                                int trace_k, float* trace_out_dev, void* stream) {
   if (!m || !trace_ids_dev || !trace_out_dev || trace_k < 1) return fail(WQ4_EINVAL, "bad trace arguments");
-  m->trace_ids = trace_ids_dev;
-  m->trace_out = trace_out_dev;
-  m->trace_s1 = max_tokens + 1;
-  m->trace_k = trace_k;
-  const wq4_status s = wa_transcribe(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, tokens_out,
-                                     n_tokens_out, stream);
-  m->trace_ids = nullptr;
-  m->trace_out = nullptr;
-  m->trace_s1 = m->trace_k = 0;
+  DecodeCall call(lang_token, max_tokens, eot_stop, false);
+  call.trace_ids = trace_ids_dev;
+  call.trace_out = trace_out_dev;
+  call.trace_s1 = max_tokens + 1;
+  call.trace_k = trace_k;
+  WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out, 1, max_tokens, n_clips));
+  WA_TRY(prepare_call(m, call));
+  const wq4_status s = transcribe_tiers(m, call, mel_dev, n_clips, tokens_out, n_tokens_out, stream, nullptr);
   for (DecGroup& g : m->groups) {  // the trace graphs bake in the caller's buffers: never replay them again
     if (g.graph) (void)hipGraphExecDestroy(g.graph);
     g.graph = nullptr;

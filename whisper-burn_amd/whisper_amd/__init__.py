@@ -146,6 +146,8 @@ def lib() -> ctypes.CDLL:
         L.wa_xattn_plan_splits.restype = c_int
         L.wa_decode_graph_key.argtypes = [vp, c_int]
         L.wa_decode_graph_key.restype = ctypes.c_longlong
+        L.wa_decode_graph_key_check.argtypes = [c_int] * 10
+        L.wa_decode_graph_key_check.restype = ctypes.c_longlong
         L.wa_xattn_kv_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
         L.wa_transcribe_trace.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, vp, c_int, vp, vp]
         L.wa_encoder_attention_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, vp]
@@ -408,6 +410,14 @@ def xattn_plan_splits(T: int, rows: int, free_cus: int) -> tuple[int, int]:
     s, c = ctypes.c_int(), ctypes.c_int()
     check(lib().wa_xattn_plan_splits(T, rows, free_cus, ctypes.byref(s), ctypes.byref(c)))
     return s.value, c.value
+
+
+def decode_graph_key_check(mode: int, lane: int, b0: int, nb: int, eot: int, trace: int, group_kv: int,
+                           range_tier: int, splits: int, residency: int) -> int:
+    """The step-graph key of these digits, most significant first (mode: scored 1
+    + timestamps 2 + sampled 4); -1 when one is outside its radix
+    (wa_decode_graph_key_check)."""
+    return int(lib().wa_decode_graph_key_check(mode, lane, b0, nb, eot, trace, group_kv, range_tier, splits, residency))
 
 
 def pipeline_unit_sizes(n_batches: int, width: int) -> list[int]:
