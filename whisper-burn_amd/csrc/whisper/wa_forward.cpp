@@ -386,6 +386,8 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
   // Q4Linear::forward at the ABI (g.atd_dec: its workspace); tier >= 1 has
   // the fold off
   float* const a32 = m->f32_attn() ? g.hid : nullptr;
+  // a prompted call's steps: the clips' first cache slots (the pad forms)
+  const int* const pad = call.prompt && state ? g.pad : nullptr;
   // y / yt = W LN(x) + bias, LN the LayerNorm (lw, lb) of the residual stream
   // g.xd: folded (wg, b2: W gamma and W beta + bias), or LayerNorm then GEMM
   auto ln_gemm = [&](const wq4_tensor* w, const float* bias, const float* wg, const float* b2, const float* lw,
@@ -417,16 +419,16 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
   };
   if (fold)
     WA_HIP(launch_embed_fold(tokens, m->tok_emb, m->dec_pos, B, Tq, D, state, pos0, g.xd, m->dec[0].ln1_w, g.atd_ln,
-                             g.ln_stats, m->ns, st));
+                             g.ln_stats, m->ns, st, pad));
   else
-    WA_HIP(launch_embed(tokens, m->tok_emb, m->dec_pos, B, Tq, D, state, pos0, g.xd, st));
+    WA_HIP(launch_embed(tokens, m->tok_emb, m->dec_pos, B, Tq, D, state, pos0, g.xd, st, pad));
   const int nl = (int)m->dec.size();
   for (int li = 0; li < nl; ++li) {  // DecoderBlock (decoder.rs:77-112 / 140-183)
     DecLayer& L = m->dec[li];
     // self-attention
     WA_TRY(ln_gemm(L.qkv, L.qkv_b, L.qkv_wg, L.qkv_b2, L.ln1_w, L.ln1_b, g.qkvd, nullptr, 0u));
     WA_HIP(launch_decoder_self_attention(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, Tq, H,
-                                         c.n_text_ctx, state, kv0, g.atd_dec, m->ns, st, a32));
+                                         c.n_text_ctx, state, kv0, g.atd_dec, m->ns, st, a32, pad));
     WA_TRY(resid_gemm(L.out, L.out_b, g.atd_dec, a32, L.ln2_w));
     // cross-attention
     WA_TRY(ln_gemm(L.cq, L.cq_b, L.cq_wg, L.cq_b2, L.ln2_w, L.ln2_b, g.qd, nullptr, 0u));
@@ -474,7 +476,7 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
 // [no_speech] and the language token's probability among the language tokens
 // -- the token from lang_idx (stride lang_stride; the detected one) or the
 // caller's lang_fixed.
-static wq4_status score_sot(wa_model* m, DecGroup& g, const float* z0, const int* lang_idx, int lang_stride, int lang_fixed,
+wq4_status score_sot(wa_model* m, DecGroup& g, const float* z0, const int* lang_idx, int lang_stride, int lang_fixed,
                      hipStream_t st) {
   const Config& c = m->cfg;
   const int B = g.nb, V = c.n_vocab;
@@ -501,7 +503,12 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStr
   const int tail = call.ts ? 1 : 2;  // prompt tokens after the language token
   std::vector<int> ptok((size_t)B * 4);
   int pos0, kv0;
-  if (lang_token >= 0) {
+  if (call.prompt) {  // the caller's prompts: one prefill pass, the scores with it
+    int P = 0;
+    WA_TRY(prefill_group(m, g, call, st, &P));
+    pos0 = P;
+    kv0 = P;
+  } else if (lang_token >= 0) {
     const int plen = 2 + tail;
     for (int b = 0; b < B; ++b) {
       ptok[b * plen + 0] = kSOT;
@@ -591,14 +598,17 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, const DecodeCall& call) {
                                 call.eot_stop ? 1 : 0, call.trace_out ? 1 : 0, m->group_kv(g) ? 1 : 0, m->range_tier,
                                 g.xplan.splits, g.xres.q, &bad);
   if (key < 0) return fail(WQ4_EINVAL, std::string("step-graph key: digit '") + bad + "' is outside its radix");
-  if (g.graph && g.graph_key == key) return WQ4_OK;
+  // a prompted call's graph runs the pad forms: kept apart beside the key
+  const bool prompted = call.prompt != nullptr;
+  if (g.graph && g.graph_key == key && g.graph_prompted == prompted) return WQ4_OK;
   // the other layouts' graphs are kept: a call goes from units of three to
   // pairs or a lone last batch, beside the masked stream and without it, and
   // the next call back again
   for (DecGroup::KeptGraph& k : g.kept)
-    if (k.exec && k.key == key) {
+    if (k.exec && k.key == key && k.prompted == prompted) {
       std::swap(g.graph, k.exec);
       std::swap(g.graph_key, k.key);
+      std::swap(g.graph_prompted, k.prompted);
       return WQ4_OK;
     }
   if (g.graph) {  // park it: in a free slot, else in place of the one parked longest ago
@@ -612,6 +622,7 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, const DecodeCall& call) {
     }
     slot->exec = g.graph;
     slot->key = g.graph_key;
+    slot->prompted = g.graph_prompted;
     g.graph = nullptr;
     g.graph_key = -1;
   }
@@ -626,6 +637,7 @@ wq4_status ensure_graph(wa_model* m, DecGroup& g, const DecodeCall& call) {
   (void)hipGraphDestroy(gr);
   if (ce != hipSuccess) return fail(WQ4_EHIP, std::string("graph instantiate: ") + hipGetErrorString(ce));
   g.graph_key = key;
+  g.graph_prompted = prompted;
   return WQ4_OK;
 }
 

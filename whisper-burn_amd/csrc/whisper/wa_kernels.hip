@@ -338,6 +338,350 @@ hipError_t launch_encoder_attention(const float* qkv, int B, int T, int H, _Floa
   return hipGetLastError();
 }
 
+// ------------------------------------ prefill attention, f16x2 MFMA --
+// The decoder's attention over a whole prompt of P rows per clip (wa_prompt.cpp):
+// encoder_attention_f16_kernel's arithmetic -- the same operand scales, the
+// same 64-key tiles in two 32-key sub-tiles, the same lazy reference maximum
+// -- over strided sources, with one difference: the sub-tiles' parts of l and
+// o are added with compensated f32 sums (1500 keys are 47 sub-tiles, where the
+// encoder's bound was set on up to 9), so its error bound holds at every T.  Query row t of clip b is
+// at q + b * q_bs + t * q_ld + head * 64, key / value j of (b, head) at k / v
+// + b * kv_bs + head * kv_hs + j * kv_ld.
+//   CAUSAL (self-attention over the qkv rows of right-aligned prompts): clip
+//     b's rows are [pad[b], P); row t attends keys [pad[b], t].  Keys are
+//     tiled from pad[b], so a clip's bits are those of an unpadded clip of
+//     P - pad[b] rows: a masked key adds exact zeros, and a sub-tile no query
+//     of the wave sees is skipped.  The workgroup also copies K and V of its
+//     rows into the head-major caches ck / cv [clip][head][ctx][64] at slots
+//     pad[b] .. P - 1 (what the decode step's kernel appends).  Pad rows are
+//     written as zeros.
+//   otherwise (cross-attention over head-major K / V): every row attends keys
+//     [0, T); pad is not read.
+// (A kernel of its own, not a mode of the encoder's: the encoder's code, and so
+// its registers and timing, stay what they were.)
+// Workgroup = 4 waves x 32 queries of one (clip, head), grid (ceil(P / 128), H, B);
+// the two tile buffers (72 KiB at two planes) let two workgroups share a CU:
+// 2 waves per SIMD, so registers are not held below 256.
+constexpr int kPfWaves = 4;
+
+template <int NS, bool CAUSAL>
+__global__ __launch_bounds__(64 * kPfWaves, 2) void prefill_attention_kernel(
+    const float* __restrict__ qp, long q_ld, long q_bs, const float* __restrict__ kp, const float* __restrict__ vp,
+    long kv_ld, long kv_hs, long kv_bs, int P, int T, const int* __restrict__ pad, int H, float* __restrict__ ck,
+    float* __restrict__ cv, int ctx, _Float16* __restrict__ tiled, float* __restrict__ out32) {
+  constexpr int NW = kPfWaves;
+  __shared__ __attribute__((aligned(16))) _Float16 klsb[2][NS][kEaKeys * kEaLd];
+  __shared__ __attribute__((aligned(16))) _Float16 vlsb[2][NS][kEaKeys * kEaLd];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l32 = lane & 31, lh = lane >> 5;
+  const int head = blockIdx.y, b = blockIdx.z;
+  const int D = H * 64;
+  const int pad_b = CAUSAL ? pad[b] : 0;
+  const int q0 = blockIdx.x * (32 * NW);
+  const int q = q0 + wave * 32 + l32;
+  const int kbp = kbp_of(D);
+  const float* kbase = kp + (size_t)b * kv_bs + (size_t)head * kv_hs + (CAUSAL ? (size_t)pad_b * kv_ld : 0);
+  const float* vbase = vp + (size_t)b * kv_bs + (size_t)head * kv_hs + (CAUSAL ? (size_t)pad_b * kv_ld : 0);
+  // the last row of this workgroup, and the keys (counted from pad_b) it reaches
+  const int qlast = min(q0 + 32 * NW, P) - 1;
+  const int nkeys = CAUSAL ? qlast - pad_b + 1 : T;
+  auto store_zero = [&]() {
+    if (q < P) {
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int gg = 0; gg < 4; ++gg)
+          attn_store4<NS>(tiled, out32, D, b * P + q, head * 64 + dt * 32 + 8 * gg + 4 * lh, kbp, 0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  if (nkeys <= 0) {  // pad rows only (workgroup-uniform)
+    store_zero();
+    return;
+  }
+  if constexpr (CAUSAL) {
+    if (ck) {  // K / V of this workgroup's real rows into the caches, bit for bit
+      for (int e = tid; e < 32 * NW * 16; e += 64 * NW) {
+        const int t = q0 + (e >> 4), s4 = (e & 15) * 4;
+        if (t >= pad_b && t < P) {
+          const size_t src = (size_t)b * kv_bs + (size_t)head * kv_hs + (size_t)t * kv_ld + s4;
+          const size_t dst = (((size_t)b * H + head) * ctx + t) * 64 + s4;
+          *reinterpret_cast<floatx4*>(ck + dst) = *reinterpret_cast<const floatx4*>(kp + src);
+          *reinterpret_cast<floatx4*>(cv + dst) = *reinterpret_cast<const floatx4*>(vp + src);
+        }
+      }
+    }
+  }
+  // the row whose query this lane carries: a pad row or a row past P carries a
+  // real row's (its result is not stored), so every lane's softmax is finite
+  const int qrow = min(max(q, pad_b), P - 1);
+  const int kend = CAUSAL ? qrow - pad_b + 1 : T;  // this lane's keys: [0, kend) from pad_b
+  // the wave's: the sub-tiles at or past it are skipped (wave-uniform)
+  const int wave_kend = CAUSAL ? min(max(q0 + wave * 32 + 31, pad_b), P - 1) - pad_b + 1 : T;
+
+  // range tier 3 (f32 output rows): values past the pair's |x| < 2047 enter at
+  // a smaller power of two, chosen from the largest |v| of the (clip, head)'s
+  // own keys -- exact, and the same for every workgroup of the clip
+  float vscale = kQKScale, pvinv = kPVInv;
+  if (out32) {
+    __shared__ float vmax_s[NW];
+    const int nall = CAUSAL ? P - pad_b : T;
+    float mx = 0.0f;
+    for (int e = tid; e < nall * 16; e += 64 * NW) {
+      const floatx4 x = *reinterpret_cast<const floatx4*>(vbase + (size_t)(e >> 4) * kv_ld + (e & 15) * 4);
+      mx = fmaxf(fmaxf(mx, fmaxf(fabsf(x[0]), fabsf(x[1]))), fmaxf(fabsf(x[2]), fabsf(x[3])));
+    }
+    mx = wave_max(mx);
+    if (lane == 0) vmax_s[wave] = mx;
+    __syncthreads();
+    mx = 0.0f;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) mx = fmaxf(mx, vmax_s[w]);
+    if (mx >= 2047.0f && mx < INFINITY) vscale = ldexpf(1.0f, 14 - ilogbf(mx));  // max |v| * vscale < 2^15
+    pvinv = 1.0f / (kPScale * vscale);
+  }
+
+  half8 qb[4][NS];
+  {
+    const float* qr = qp + (size_t)b * q_bs + (size_t)qrow * q_ld + head * 64;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      const floatx4 x0 = *reinterpret_cast<const floatx4*>(qr + 16 * ks + 8 * lh);
+      const floatx4 x1 = *reinterpret_cast<const floatx4*>(qr + 16 * ks + 8 * lh + 4);
+      half8 hi, lo;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float v = (j < 4 ? x0[j] : x1[j - 4]) * kEaQScale;
+        _Float16 a, c;
+        split_f16(v * kQKScale, a, c);
+        hi[j] = a;
+        lo[j] = c;
+      }
+      qb[ks][0] = hi;
+      if constexpr (NS == 2) qb[ks][1] = lo;
+    }
+  }
+  // staging: thread (key tid / TPK, dims EPT (tid % TPK) + 0..EPT-1) of K and V
+  constexpr int EPT = 64 * kEaKeys / (64 * NW);
+  constexpr int TPK = 64 / EPT;
+  const int skey = tid / TPK, sd = (tid % TPK) * EPT;
+  floatx4 kreg[EPT / 4], vreg[EPT / 4];
+  auto fetch = [&](int key0) {
+    const int key = key0 + skey;
+    const bool ok = key < nkeys;
+    const size_t ofs = (size_t)(ok ? key : 0) * kv_ld + sd;
+#pragma unroll
+    for (int i = 0; i < EPT / 4; ++i) {
+      kreg[i] = ok ? *reinterpret_cast<const floatx4*>(kbase + ofs + 4 * i) : floatx4{0.f, 0.f, 0.f, 0.f};
+      vreg[i] = ok ? *reinterpret_cast<const floatx4*>(vbase + ofs + 4 * i) : floatx4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  auto stage = [&](int buf) {
+    _Float16(*kls)[kEaKeys * kEaLd] = klsb[buf];
+    _Float16(*vls)[kEaKeys * kEaLd] = vlsb[buf];
+    half8 kh[EPT / 8], kl[EPT / 8], vh[EPT / 8], vl[EPT / 8];
+#pragma unroll
+    for (int i = 0; i < EPT; i += 2) {
+      ea_half2 h2, l2;
+      split2(kreg[i >> 2][i & 3] * kQKScale, kreg[i >> 2][(i & 3) + 1] * kQKScale, h2, l2);
+      kh[i >> 3][i & 7] = h2[0];
+      kh[i >> 3][(i & 7) + 1] = h2[1];
+      kl[i >> 3][i & 7] = l2[0];
+      kl[i >> 3][(i & 7) + 1] = l2[1];
+      split2(vreg[i >> 2][i & 3] * vscale, vreg[i >> 2][(i & 3) + 1] * vscale, h2, l2);
+      vh[i >> 3][i & 7] = h2[0];
+      vh[i >> 3][(i & 7) + 1] = h2[1];
+      vl[i >> 3][i & 7] = l2[0];
+      vl[i >> 3][(i & 7) + 1] = l2[1];
+    }
+#pragma unroll
+    for (int u = 0; u < EPT / 8; ++u) {
+      *reinterpret_cast<half8*>(&kls[0][skey * kEaLd + sd + 8 * u]) = kh[u];
+      *reinterpret_cast<half8*>(&vls[0][skey * kEaLd + sd + 8 * u]) = vh[u];
+      if constexpr (NS == 2) {
+        *reinterpret_cast<half8*>(&kls[NS - 1][skey * kEaLd + sd + 8 * u]) = kl[u];
+        *reinterpret_cast<half8*>(&vls[NS - 1][skey * kEaLd + sd + 8 * u]) = vl[u];
+      }
+    }
+  };
+
+  // l and o are sums over up to 47 sub-tiles (T = 1500): each sub-tile's part
+  // is formed on its own and added with a compensated (two-sum) f32 add, lc /
+  // oc the running compensations, so the sums' rounding does not grow with T
+  float m = -INFINITY, l = 0.0f, lc = 0.0f;
+  floatx16 o[2], oc[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    o[0][i] = 0.0f;
+    o[1][i] = 0.0f;
+    oc[0][i] = 0.0f;
+    oc[1][i] = 0.0f;
+  }
+  auto two_sum = [](float& s, float& c, float x) {
+    const float t = s + x, bp = t - s;
+    c += (s - (t - bp)) + (x - bp);
+    s = t;
+  };
+  const int g = lane >> 4, gi = lane & 15;
+  const int trow = 4 * (g >> 1) + (gi >> 2), tcol = 16 * (g & 1) + 4 * (gi & 3);
+  const int ntile = (nkeys + kEaKeys - 1) / kEaKeys;
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  if (ntile > 1) fetch(kEaKeys);
+  for (int kt = 0; kt < ntile; ++kt) {
+    const int key0 = kt * kEaKeys;
+    const _Float16(*kls)[kEaKeys * kEaLd] = klsb[kt & 1];
+    const _Float16(*vls)[kEaKeys * kEaLd] = vlsb[kt & 1];
+#pragma unroll
+    for (int sub = 0; sub < kEaKeys / 32; ++sub) {
+      if (key0 + sub * 32 >= wave_kend) continue;  // no query of this wave sees these keys
+      floatx16 st;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) st[i] = 0.0f;
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const int off = (sub * 32 + l32) * kEaLd + 16 * ks + 8 * lh;
+        const half8 ah = *reinterpret_cast<const half8*>(&kls[0][off]);
+        st = ea_mfma(ah, qb[ks][0], st);
+        if constexpr (NS == 2) {
+          const half8 al = *reinterpret_cast<const half8*>(&kls[1][off]);
+          st = ea_mfma(al, qb[ks][0], st);
+          st = ea_mfma(ah, qb[ks][1], st);
+        }
+      }
+      if (CAUSAL || key0 + sub * 32 + 32 > T) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = key0 + sub * 32 + (i & 3) + 8 * (i >> 2) + 4 * lh;
+          if (key >= kend) st[i] = -INFINITY;
+        }
+      }
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) mx = fmaxf(mx, st[i]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      // lazy reference maximum, as the encoder's kernel; a sub-tile wholly
+      // masked for this lane leaves m, l and o as they are (alpha 1, p 0)
+      float mn = fmaxf(m, mx);
+      if (m != -INFINITY && mn - m <= kEaLazyMax) mn = m;
+      const float alpha = __builtin_amdgcn_exp2f((m - mn) * kSInv);
+      float rs = 0.0f;
+      // mn is finite: key 0 is visible to every lane (kend >= 1) and in the first sub-tile
+      const float nmn = -mn * kSInv;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        st[i] = __builtin_amdgcn_exp2f(fmaf(st[i], kSInv, nmn));
+        rs += st[i];
+      }
+      rs += __shfl_xor(rs, 32, 64);
+      m = mn;
+      if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+        l *= alpha;
+        lc *= alpha;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          o[0][i] *= alpha;
+          o[1][i] *= alpha;
+          oc[0][i] *= alpha;
+          oc[1][i] *= alpha;
+        }
+      }
+      two_sum(l, lc, rs);
+      floatx16 od[2];  // this sub-tile's P V
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        od[0][i] = 0.0f;
+        od[1][i] = 0.0f;
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        half8 ph, pl;
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+          ea_half2 h2, l2;
+          split2(st[8 * t + j] * kPScale, st[8 * t + j + 1] * kPScale, h2, l2);
+          ph[j] = h2[0];
+          ph[j + 1] = h2[1];
+          pl[j] = l2[0];
+          pl[j + 1] = l2[1];
+        }
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt) {
+          half8 va[NS];
+#pragma unroll
+          for (int pp = 0; pp < NS; ++pp) {
+            const _Float16* vb = &vls[pp][(sub * 32 + 16 * t + trow) * kEaLd + dt * 32 + tcol];
+            const ea_half4 x0 = ea_tr4(vb);
+            const ea_half4 x1 = ea_tr4(vb + 8 * kEaLd);
+            va[pp] = half8{x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+          }
+          od[dt] = ea_mfma(va[0], ph, od[dt]);
+          if constexpr (NS == 2) {
+            od[dt] = ea_mfma(va[1], ph, od[dt]);
+            od[dt] = ea_mfma(va[0], pl, od[dt]);
+          }
+        }
+      }
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt) {  // two_sum, element-wise
+        const floatx16 t = o[dt] + od[dt], bp = t - o[dt];
+        oc[dt] += (o[dt] - (t - bp)) + (od[dt] - bp);
+        o[dt] = t;
+      }
+    }
+    if (kt + 1 < ntile) {
+      stage((kt + 1) & 1);
+      if (kt + 2 < ntile) fetch(key0 + 2 * kEaKeys);
+    }
+    __syncthreads();
+  }
+  if (q < pad_b) {
+    store_zero();
+  } else if (q < P) {
+    const int row = b * P + q;
+    const float inv = (1.0f / (l + lc)) * pvinv;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      o[0][i] += oc[0][i];
+      o[1][i] += oc[1][i];
+    }
+#pragma unroll
+    for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+      for (int gg = 0; gg < 4; ++gg) {
+        const int d = dt * 32 + 8 * gg + 4 * lh;
+        attn_store4<NS>(tiled, out32, D, row, head * 64 + d, kbp, o[dt][4 * gg] * inv, o[dt][4 * gg + 1] * inv,
+                        o[dt][4 * gg + 2] * inv, o[dt][4 * gg + 3] * inv);
+      }
+  }
+}
+
+hipError_t launch_prefill_self_attention(const float* qkv, float* cache_k, float* cache_v, int B, int P, int H, int ctx,
+                                         const int* pad, _Float16* tiled, int ns, hipStream_t st, float* out32) {
+  if (B < 1 || P < 1 || H < 1 || !qkv || !pad || (cache_k && (P > ctx || !cache_v))) return hipErrorInvalidValue;
+  const long D = 64L * H;
+  const dim3 grid((P + 32 * kPfWaves - 1) / (32 * kPfWaves), H, B), block(64 * kPfWaves);
+#define WA_PFS(NS_)                                                                                                \
+  hipLaunchKernelGGL((prefill_attention_kernel<NS_, true>), grid, block, 0, st, qkv, 3 * D, P * 3 * D, qkv + D,    \
+                     qkv + 2 * D, 3 * D, 64L, P * 3 * D, P, P, pad, H, cache_k, cache_v, ctx, tiled, out32)
+  if (ns == 2) { WA_PFS(2); } else { WA_PFS(1); }
+#undef WA_PFS
+  return hipGetLastError();
+}
+
+hipError_t launch_prefill_cross_attention(const float* q, const float* k, const float* v, int B, int P, int T, int H,
+                                          _Float16* tiled, int ns, hipStream_t st, float* out32) {
+  if (B < 1 || P < 1 || T < 1 || H < 1 || !q || !k || !v) return hipErrorInvalidValue;
+  const long D = 64L * H;
+  const dim3 grid((P + 32 * kPfWaves - 1) / (32 * kPfWaves), H, B), block(64 * kPfWaves);
+#define WA_PFX(NS_)                                                                                               \
+  hipLaunchKernelGGL((prefill_attention_kernel<NS_, false>), grid, block, 0, st, q, D, P * D, k, v, 64L, 64L * T, \
+                     64L * T * H, P, T, nullptr, H, nullptr, nullptr, 0, tiled, out32)
+  if (ns == 2) { WA_PFX(2); } else { WA_PFX(1); }
+#undef WA_PFX
+  return hipGetLastError();
+}
+
 // ---------------------------------------------- decode-step attention --
 // Shared by self- and cross-attention of the decoder (Tq <= 4 queries per
 // clip): 16 lanes share one key (4 dims each), 4 keys per load instruction,
@@ -467,12 +811,17 @@ template <int NS, int TQ>
 __global__ __launch_bounds__(256) void dec_self_attn_kernel(const float* __restrict__ qkv, float* __restrict__ ck,
                                                             float* __restrict__ cv, int Tq_, int H, int ctx,
                                                             const DecodeState* state, int kv_len_host,
+                                                            const int* __restrict__ pad,
                                                             _Float16* __restrict__ tiled, float* __restrict__ out32) {
   const int Tq = TQ == 1 ? 1 : Tq_;
   __shared__ float wm[4][TQ], wl[4][TQ];
   __shared__ float wo[4][TQ][64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int head = blockIdx.x, b = blockIdx.y;
+  // a right-aligned prompt (wa_prefill): the clip's entries start at slot
+  // pad_b, and the waves split the keys counted from there -- the order of
+  // operations of an unpadded clip with kv_len - pad_b entries
+  const int pad_b = pad ? pad[b] : 0;
   const int D = H * 64;
   const int sub = lane & 15, grp = lane >> 4;
   const int kv_len = state ? state->kv_len : kv_len_host;
@@ -494,9 +843,9 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const float* __restr
     qv[t] = t < Tq ? *reinterpret_cast<const floatx4*>(qkv + (size_t)(b * Tq + t) * 3 * D + head * 64 + sub * 4) *
                          kEaQScale
                    : floatx4{0.f, 0.f, 0.f, 0.f};
-  const int nk = kv_len + Tq;
+  const int nk = kv_len + Tq - pad_b;
   const int per_wave = (nk + 3) / 4;
-  const int k0 = min(nk, wave * per_wave), k1 = min(nk, k0 + per_wave);
+  const int k0 = pad_b + min(nk, wave * per_wave), k1 = min(pad_b + nk, k0 + per_wave);
   float m[TQ], l[TQ];
   floatx4 o[TQ];
   attn_scan<TQ, 8>(
@@ -523,12 +872,12 @@ __global__ __launch_bounds__(256) void dec_self_attn_kernel(const float* __restr
 
 hipError_t launch_decoder_self_attention(const float* qkv, float* cache_k, float* cache_v, int B, int Tq, int H,
                                          int ctx, const DecodeState* state, int kv_len_host, _Float16* tiled,
-                                         int ns, hipStream_t st, float* out32) {
+                                         int ns, hipStream_t st, float* out32, const int* pad) {
   if (Tq > 4 || ctx > kMaxCtx) return hipErrorInvalidValue;
   const dim3 grid(H, B), block(256);
 #define WA_SELF(NS_, TQ_)                                                                                     \
   hipLaunchKernelGGL((dec_self_attn_kernel<NS_, TQ_>), grid, block, 0, st, qkv, cache_k, cache_v, Tq, H, ctx, \
-                     state, kv_len_host, tiled, out32)
+                     state, kv_len_host, pad, tiled, out32)
   if (ns == 2) {
     if (Tq == 1) { WA_SELF(2, 1); } else { WA_SELF(2, 4); }
   } else {
@@ -812,19 +1161,21 @@ hipError_t launch_conv_gelu(const float* in, long in_bs, long in_cs, long in_ts,
 // ----------------------------------------------------------- embedding --
 __global__ void embed_kernel(const int* __restrict__ tokens, const float* __restrict__ te,
                              const float* __restrict__ pe, int Tq, int D, const DecodeState* state, int pos0,
-                             float* __restrict__ x) {
+                             const int* __restrict__ pad, float* __restrict__ x) {
   const int row = blockIdx.x;  // b * Tq + t
   const int t = row % Tq;
-  const int p = (state ? state->position : pos0) + t;
+  // a right-aligned prompt: the clip's positions count from its slot pad[b]
+  // (a pad row of the prefill: position 0, never read by a real row)
+  const int p = max(0, (state ? state->position : pos0) + t - (pad ? pad[row / Tq] : 0));
   const int tok = tokens[row];
   for (int d = threadIdx.x; d < D; d += blockDim.x)
     x[(size_t)row * D + d] = te[(size_t)tok * D + d] + pe[(size_t)p * D + d];
 }
 
 hipError_t launch_embed(const int* tokens, const float* tok_emb, const float* pos_emb, int B, int Tq, int D,
-                        const DecodeState* state, int pos0_host, float* x, hipStream_t st) {
+                        const DecodeState* state, int pos0_host, float* x, hipStream_t st, const int* pad) {
   hipLaunchKernelGGL(embed_kernel, dim3(B * Tq), dim3(256), 0, st, tokens, tok_emb, pos_emb, Tq, D, state,
-                     pos0_host, x);
+                     pos0_host, pad, x);
   return hipGetLastError();
 }
 
@@ -836,12 +1187,13 @@ hipError_t launch_embed(const int* tokens, const float* tok_emb, const float* po
 template <int NS>
 __global__ __launch_bounds__(256) void embed_fold_kernel(const int* __restrict__ tokens, const float* __restrict__ te,
                                                          const float* __restrict__ pe, int Tq, int D,
-                                                         const DecodeState* state, int pos0, float* __restrict__ x,
+                                                         const DecodeState* state, int pos0,
+                                                         const int* __restrict__ pad, float* __restrict__ x,
                                                          const float* __restrict__ gamma, _Float16* __restrict__ at,
                                                          float* __restrict__ stats) {
   const int row = blockIdx.x;  // b * Tq + t
   const int t = row % Tq;
-  const int p = (state ? state->position : pos0) + t;
+  const int p = max(0, (state ? state->position : pos0) + t - (pad ? pad[row / Tq] : 0));  // as embed_kernel
   const int tok = tokens[row];
   const int kbp = kbp_of(D);
   for (int c = 4 * threadIdx.x; c < ((D + 1023) / 1024) * 1024; c += 1024) {
@@ -875,14 +1227,14 @@ __global__ __launch_bounds__(256) void embed_fold_kernel(const int* __restrict__
 
 hipError_t launch_embed_fold(const int* tokens, const float* tok_emb, const float* pos_emb, int B, int Tq, int D,
                              const DecodeState* state, int pos0_host, float* x, const float* gamma, _Float16* at,
-                             float* stats, int ns, hipStream_t st) {
+                             float* stats, int ns, hipStream_t st, const int* pad) {
   if (D % 32 != 0) return hipErrorInvalidValue;
   if (ns == 2)
     hipLaunchKernelGGL(embed_fold_kernel<2>, dim3(B * Tq), dim3(256), 0, st, tokens, tok_emb, pos_emb, Tq, D, state,
-                       pos0_host, x, gamma, at, stats);
+                       pos0_host, pad, x, gamma, at, stats);
   else
     hipLaunchKernelGGL(embed_fold_kernel<1>, dim3(B * Tq), dim3(256), 0, st, tokens, tok_emb, pos_emb, Tq, D, state,
-                       pos0_host, x, gamma, at, stats);
+                       pos0_host, pad, x, gamma, at, stats);
   return hipGetLastError();
 }
 

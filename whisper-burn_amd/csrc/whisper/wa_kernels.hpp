@@ -29,9 +29,27 @@ hipError_t launch_encoder_attention(const float* qkv, int B, int T, int H, _Floa
 // appends k, v of the Tq new tokens at cache index kv_len (+ kv_base_extra)
 // and attends over kv_len + Tq entries, causal inside the new tokens when
 // Tq > 1 (attention.rs:270-287).  cache_k/v: [B, ctx, D].
+// pad (nullable; device [B]): clip b's entries start at cache slot pad[b] (a
+// right-aligned prompt, launch_prefill_self_attention) -- keys [pad[b],
+// kv_len + Tq), split over the waves from pad[b], so the clip's bits are those
+// of an unpadded clip with kv_len - pad[b] entries.
 hipError_t launch_decoder_self_attention(const float* qkv, float* cache_k, float* cache_v, int B, int Tq, int H,
                                          int ctx, const DecodeState* state, int kv_len_host, _Float16* tiled,
-                                         int ns, hipStream_t st, float* out32 = nullptr);
+                                         int ns, hipStream_t st, float* out32 = nullptr, const int* pad = nullptr);
+
+// The decoder's attention over whole prompts of P rows per clip, flash-style
+// on f16-pair MFMAs (the encoder kernel's arithmetic).
+// Self-attention: qkv [B*P, 3D]; clip b's prompt is right-aligned in rows
+// [pad[b], P) (pad: device [B], each in [0, P)); row t attends keys [pad[b], t]
+// and K / V of the real rows are copied into the head-major caches at slots
+// pad[b] .. P - 1 (cache_k null: no copy).  Pad rows are written as zeros.
+hipError_t launch_prefill_self_attention(const float* qkv, float* cache_k, float* cache_v, int B, int P, int H, int ctx,
+                                         const int* pad, _Float16* tiled, int ns, hipStream_t st,
+                                         float* out32 = nullptr);
+// Cross-attention: q [B*P, D], k / v head-major [B][H][T][64] f32; every row
+// attends all T keys (each clip's K / V are read once per 128 rows).
+hipError_t launch_prefill_cross_attention(const float* q, const float* k, const float* v, int B, int P, int T, int H,
+                                          _Float16* tiled, int ns, hipStream_t st, float* out32 = nullptr);
 
 // Cross-attention over cached K / V (attention.rs:177-236, the reference's
 // form; used for decode groups of a few clips): q [B*Tq, D] f32, k / v
@@ -106,16 +124,18 @@ hipError_t launch_conv_gelu(const float* in, long in_bs, long in_cs, long in_ts,
                             hipStream_t st);
 
 // x[b*Tq + t] = tok_emb[tokens[b*Tq + t]] + pos_emb[pos0 + t]   (decoder.rs:326-343)
-// pos0 = state ? state->position : pos0_host.
+// pos0 = state ? state->position : pos0_host.  pad (nullable; device [B]): clip
+// b's positions count from its first slot, pos0 + t - pad[b] (a right-aligned
+// prompt; a pad row, where that is negative, gets position 0).
 hipError_t launch_embed(const int* tokens, const float* tok_emb, const float* pos_emb, int B, int Tq, int D,
-                        const DecodeState* state, int pos0_host, float* x, hipStream_t st);
+                        const DecodeState* state, int pos0_host, float* x, hipStream_t st, const int* pad = nullptr);
 
 // launch_embed + the LayerNorm-fold producer for gamma (wq4_gemm_tiled_lnfold):
 // also writes at = A-tiled x * gamma and stats [rows][D/16][2] (mean and sum
 // of squared deviations of each 16-column tile of x); D % 32 == 0.
 hipError_t launch_embed_fold(const int* tokens, const float* tok_emb, const float* pos_emb, int B, int Tq, int D,
                              const DecodeState* state, int pos0_host, float* x, const float* gamma, _Float16* at,
-                             float* stats, int ns, hipStream_t st);
+                             float* stats, int ns, hipStream_t st, const int* pad = nullptr);
 
 }  // namespace wa
 

@@ -15,6 +15,7 @@ struct wa_long_result {
     wa_long_window w;
     std::vector<int32_t> tokens;  // n_tokens
     std::vector<float> logprob;   // max_tokens + 1 slots
+    int prompt_len = 0;           // previous-text tokens in the window's prompt (wa_transcribe_long_prompted)
   };
   struct Stream {
     std::vector<Window> windows;
@@ -78,8 +79,44 @@ wq4_status wa_long_round(const int32_t* content, const int32_t* seek, const int3
   return WQ4_OK;
 }
 
-wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams, const int64_t* offset,
-                              const int64_t* n_samples, const wa_long_options* o, wa_long_result** out, void* stream) {
+wq4_status wa_long_prompt_window(const int32_t* prev, int n_prev, int reset, int n_text_ctx, int max_tokens,
+                                 int startofprev, int lang_token, int task_token, int32_t* prompt, int cap, int* n,
+                                 int* k_out) {
+  if (!n || !k_out || n_prev < 0 || (n_prev > 0 && !prev) || reset < 0 || reset > n_prev || cap < 0 ||
+      (cap > 0 && !prompt))
+    return fail(WQ4_EINVAL, "bad arguments");
+  if (n_text_ctx < 8 || max_tokens < 1 || max_tokens > n_text_ctx - 4)
+    return fail(WQ4_EINVAL, "need n_text_ctx >= 8 and max_tokens in [1, n_text_ctx - 4]");
+  const int k = std::max(0, std::min({n_prev - reset, n_text_ctx / 2 - 1, n_text_ctx - 4 - max_tokens}));
+  std::vector<int32_t> p;
+  if (k > 0) {
+    p.push_back(startofprev);
+    p.insert(p.end(), prev + n_prev - k, prev + n_prev);
+  }
+  p.insert(p.end(), {50258, lang_token, task_token});
+  *k_out = k;
+  return copy_out(p, prompt, cap, n, "prompt");
+}
+
+wq4_status wa_long_prompt_next(int32_t* prev, int* n_prev, int* reset, const int32_t* tokens, int n, int ts0,
+                               int skipped, float temperature, int condition_on_previous_text,
+                               float reset_temperature) {
+  if (!n_prev || !reset || *n_prev < 0 || n < 0 || (n > 0 && !tokens) || (*n_prev + n > 0 && !prev))
+    return fail(WQ4_EINVAL, "bad arguments");
+  if (skipped) return WQ4_OK;
+  int n_segs = 0, seek_frames = 0;
+  std::vector<wa_segment> segs(std::max(1, n));
+  WA_TRY(wa_segments_from_tokens(tokens, n, ts0, segs.data(), (int)segs.size(), &n_segs, &seek_frames));
+  for (int i = 0; i < n_segs; ++i)
+    for (int t = segs[i].tok_begin; t < segs[i].tok_end; ++t) prev[(*n_prev)++] = tokens[t];
+  if (!condition_on_previous_text || temperature > reset_temperature) *reset = *n_prev;
+  return WQ4_OK;
+}
+
+// wa_transcribe_long; lp non-null: with the prompt handling of wa_transcribe_long_prompted.
+static wq4_status long_run(wa_model* m, const float* audio_dev, int n_streams, const int64_t* offset,
+                           const int64_t* n_samples, const wa_long_options* o, const wa_long_prompt* lp,
+                           wa_long_result** out, void* stream) {
   if (out) *out = nullptr;
   if (!m || !audio_dev || !offset || !n_samples || !o || !out || !o->temperatures || !o->seed)
     return fail(WQ4_EINVAL, "null argument");
@@ -92,12 +129,37 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
   for (int r = 0; r < n_streams; ++r)
     if (offset[r] < 0 || n_samples[r] < 0 || n_samples[r] >= kMelLongMaxSamples)
       return fail(WQ4_EINVAL, "need offset >= 0 and 0 <= n_samples < 160 * (2^31 - 3001)");
+  const int ctx = m->cfg.n_text_ctx, V = m->cfg.n_vocab;
+  if (lp) {
+    if (o->lang_token < 0 || o->lang_token >= V)
+      return fail(WQ4_EINVAL, "a prompted long-form call needs lang_token in [0, n_vocab)");
+    if (lp->ld < 0 || (lp->ld > 0 && (!lp->initial || !lp->n_initial))) return fail(WQ4_EINVAL, "bad initial prompts");
+    if (!std::isfinite(lp->reset_temperature)) return fail(WQ4_EINVAL, "reset_temperature must be finite");
+    if (o->max_tokens > ctx - 4) return fail(WQ4_EINVAL, "max_tokens + the 3-token prompt must fit n_text_ctx");
+    for (int r = 0; lp->ld > 0 && r < n_streams; ++r) {
+      if (lp->n_initial[r] < 0 || lp->n_initial[r] > lp->ld) return fail(WQ4_EINVAL, "n_initial must be in [0, ld]");
+      for (int i = 0; i < lp->n_initial[r]; ++i)
+        if (lp->initial[(size_t)r * lp->ld + i] < 0 || lp->initial[(size_t)r * lp->ld + i] >= V)
+          return fail(WQ4_EINVAL, "initial prompt token id outside [0, n_vocab)");
+    }
+  }
 
   const int S = n_streams, T = o->max_tokens, n_mels = m->cfg.n_mels, ts0 = m->ts0();
   const size_t slots = (size_t)T + 1;
   const int bmax = std::min(m->bmax, S);
   // every round's ladder: sampled, with timestamps, stopping at EOT
-  const DecodeCall call(o->lang_token, T, 1, true, true, o->max_initial, true);
+  DecodeCall call(o->lang_token, T, 1, true, true, o->max_initial, true);
+  // the recordings' previous text and reset marks, and one round's prompts
+  // ([startofprev] + at most ctx / 2 - 1 ids + [SOT, lang, TRANSCRIBE])
+  const int pld = ctx / 2 + 3;
+  std::vector<std::vector<int32_t>> prev(lp ? S : 0);
+  std::vector<int> reset(S, 0);
+  for (int r = 0; lp && lp->ld > 0 && r < S; ++r)
+    prev[r].assign(lp->initial + (size_t)r * lp->ld, lp->initial + (size_t)r * lp->ld + lp->n_initial[r]);
+  std::vector<int32_t> p_tok(lp ? (size_t)std::min(m->bmax, S) * pld : 0), p_n(lp ? std::min(m->bmax, S) : 0);
+  std::vector<int> p_k(std::min(m->bmax, S), 0);
+  const wa_prompt round_prompt{p_tok.data(), p_n.data(), pld};
+  if (lp) call.prompt = &round_prompt;
   WA_HIP(hipSetDevice(m->device));
   Dev d;
   float* max_dev = d.alloc<float>(S);
@@ -115,8 +177,8 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
   std::vector<int64_t> c_off(bmax), c_n(bmax);
   std::vector<int32_t> c_seek(bmax), c_max(bmax), tok((size_t)bmax * T), nt(bmax), lt(bmax), rung(bmax);
   std::vector<uint64_t> c_seed(bmax);
-  std::vector<float> lp((size_t)bmax * slots), ns(bmax), lpr(bmax);
-  const wa_scores scores{lp.data(), ns.data(), lt.data(), lpr.data()};
+  std::vector<float> lpv((size_t)bmax * slots), ns(bmax), lpr(bmax);
+  const wa_scores scores{lpv.data(), ns.data(), lt.data(), lpr.data()};
   wa_fallback fb{};
   fb.temperatures = o->temperatures;
   fb.n_temperatures = o->n_temperatures;
@@ -139,7 +201,16 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
     }
     WA_TRY(wa_long_mel_windows(m->device, audio_dev, B, c_off.data(), c_n.data(), c_seek.data(), c_max.data(),
                                max_dev, n_mels, mel_dev, stream));
+    for (int c = 0; lp && c < B; ++c) {
+      const int r = rec[c];
+      int n = 0;
+      WA_TRY(wa_long_prompt_window(prev[r].data(), (int)prev[r].size(), reset[r], ctx, T,
+                                   m->cfg.no_timestamps_token() - 2, o->lang_token, m->cfg.transcribe_token(),
+                                   p_tok.data() + (size_t)c * pld, pld, &n, &p_k[c]));
+      p_n[c] = n;
+    }
     WA_TRY(prepare_call(m, call));  // the first round allocates the mode's buffers
+    if (lp) WA_TRY(ensure_prefill(m));
     WA_TRY(transcribe_ladder(m, call, mel_dev, B, &fb, tok.data(), nt.data(), &scores, rung.data(), stream));
     for (int i = 0; i < 5; ++i) sums[i] += m->timings[i];
     for (int c = 0; c < B; ++c) {
@@ -147,7 +218,7 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
       wa_long_result::Stream& rs = res->streams[r];
       wa_long_result::Window win;
       const int32_t* toks = tok.data() + (size_t)c * T;
-      const float* lps = lp.data() + c * slots;
+      const float* lps = lpv.data() + c * slots;
       double sum = 0.0;
       int cnt = 0;
       for (size_t i = 0; i < slots; ++i)
@@ -180,6 +251,15 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
                                                 w.seek * 0.01 + (double)segs[i].start_s,
                                                 w.seek * 0.01 + (double)segs[i].end_s});
       }
+      if (lp) {
+        std::vector<int32_t>& pv = prev[r];
+        int np = (int)pv.size();
+        pv.resize((size_t)np + nt[c]);
+        WA_TRY(wa_long_prompt_next(pv.data(), &np, &reset[r], toks, nt[c], ts0, skipped, w.temperature,
+                                   lp->condition_on_previous_text, lp->reset_temperature));
+        pv.resize(np);
+        win.prompt_len = p_k[c];
+      }
       win.tokens.assign(toks, toks + nt[c]);
       win.logprob.assign(lps, lps + slots);
       rs.windows.push_back(std::move(win));
@@ -190,6 +270,31 @@ wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams
   for (int r = 0; r < S; ++r) res->streams[r].truncated = seek[r] < content[r];
   std::memcpy(m->timings, sums, sizeof(sums));
   *out = res.release();
+  return WQ4_OK;
+}
+
+wq4_status wa_transcribe_long(wa_model* m, const float* audio_dev, int n_streams, const int64_t* offset,
+                              const int64_t* n_samples, const wa_long_options* o, wa_long_result** out, void* stream) {
+  return long_run(m, audio_dev, n_streams, offset, n_samples, o, nullptr, out, stream);
+}
+
+wq4_status wa_transcribe_long_prompted(wa_model* m, const float* audio_dev, int n_streams, const int64_t* offset,
+                                       const int64_t* n_samples, const wa_long_options* o, const wa_long_prompt* lp,
+                                       wa_long_result** out, void* stream) {
+  // no prompt at all: the existing path (once the prompted call's own arguments are checked)
+  bool any = lp && lp->condition_on_previous_text;
+  for (int r = 0; lp && !any && lp->ld > 0 && lp->n_initial && r < n_streams; ++r) any = lp->n_initial[r] > 0;
+  if (lp && !any && o && o->lang_token < 0) {
+    if (out) *out = nullptr;
+    return fail(WQ4_EINVAL, "a prompted long-form call needs lang_token >= 0");
+  }
+  return long_run(m, audio_dev, n_streams, offset, n_samples, o, any ? lp : nullptr, out, stream);
+}
+
+wq4_status wa_long_result_prompt_len(const wa_long_result* r, int stream, int index, int* k) {
+  const wa_long_result::Stream* s = stream_of(r, stream);
+  if (!s || index < 0 || index >= (int)s->windows.size() || !k) return fail(WQ4_EINVAL, "bad arguments");
+  *k = s->windows[index].prompt_len;
   return WQ4_OK;
 }
 

@@ -162,18 +162,25 @@ struct DecGroup {
   float* smp_temp = nullptr;
   uint64_t* smp_seed = nullptr;
   int clip0 = 0;  // this group's first clip in the call's per-clip host arrays (run_decode)
+  // prompted transcribes (wa_transcribe_prompted; allocated by the first one,
+  // ensure_prefill): the clips' first cache slots [nb] -- prompts are
+  // right-aligned to the group's longest -- read by the prefill and by the pad
+  // forms of the step's embedding and self-attention
+  int* pad = nullptr;
   DecodeState* state;
   void* ffn_ws = nullptr;  // range tier 2: wq4_ffn_forward_ws workspace (4 * nb rows)
   size_t ffn_ws_bytes = 0;
   int* host_ndone = nullptr;  // pinned ring
   hipGraphExec_t graph = nullptr;
   int64_t graph_key = -1;  // wa::graph_key of the layout and mode the graph was captured for
+  bool graph_prompted = false;  // beside the key: the graph runs the pad forms (a prompted call's)
   // graphs of other layouts this group ran (ensure_graph): a call of units of
   // three and two, with and without the masked stream beside them, goes
   // through four keys per group and comes back to each
   struct KeptGraph {
     hipGraphExec_t exec = nullptr;
     int64_t key = -1;
+    bool prompted = false;
   };
   KeptGraph kept[kKeptGraphs];
   int kept_next = 0;  // the slot the next parked graph replaces once all are taken
@@ -199,6 +206,11 @@ struct DecodeCall {
   const float* temp = nullptr;
   const uint64_t* seed = nullptr;
   const uint8_t* frozen = nullptr;
+  // prompted calls (wa_transcribe_prompted; null otherwise): the clips' own
+  // prompts, host arrays over the call's clips like the ones above.  The
+  // prompt of every group is then one prefill pass and its steps run the pad
+  // forms; lang_token is not read.
+  const wa_prompt* prompt = nullptr;
   // decode-step logit trace (wa_transcribe_trace; null otherwise): device
   // [clip][trace_s1][trace_k] ids and their logits
   const int* trace_ids = nullptr;
@@ -328,6 +340,21 @@ struct wa_model {
   bool f32_attn() const { return range_tier >= 3; }
   void* ffn_ws = nullptr;
   size_t ffn_ws_bytes = 0;
+  // The prefill of prompted calls (wa_prompt.cpp): activations for bmax *
+  // n_text_ctx rows.  They borrow the encoder's buffers, idle while a
+  // sequential call decodes -- x / q / hid in h1, qkv in qkv, the two A-tiled
+  // operands in at_f (m->x and m->at_d stay: they feed the K / V GEMMs) -- and
+  // the groups of a call run their prefills one after another.  tok: the
+  // right-aligned prompt ids; xk / xv: one layer's cross-attention K / V of
+  // the clips of a group without the few-clip caches (allocated when first
+  // needed).
+  struct Prefill {
+    bool ok = false;
+    float *x = nullptr, *qkv = nullptr, *q = nullptr, *hid = nullptr;
+    _Float16 *atd = nullptr, *atf = nullptr;
+    int* tok = nullptr;
+    float *xk = nullptr, *xv = nullptr;
+  } pf;
   float timings[5] = {0, 0, 0, 0, 0};
   // every group's score / timestamp / sampling buffers are allocated
   // (prepare_call: by the first call in that mode, all or nothing)
@@ -415,6 +442,20 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
                            const DecodeState* state, int pos0, int kv0, hipStream_t st);
 wq4_status prompt_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st);
 wq4_status ensure_graph(wa_model* m, DecGroup& g, const DecodeCall& call);
+// the SOT-position scores of prompt_group (wa_prompt.cpp takes them at ragged rows)
+wq4_status score_sot(wa_model* m, DecGroup& g, const float* z0, const int* lang_idx, int lang_stride, int lang_fixed,
+                     hipStream_t st);
+
+// ---- wa_prompt.cpp
+// The arguments of a prompted call (null pointers, n_tokens in [1, ld], ids in
+// [0, n_vocab), max n_tokens + max_tokens <= n_text_ctx), on the host.
+wq4_status check_prompt(const wa_model* m, const wa_prompt* p, int n_clips, int max_tokens);
+wq4_status ensure_prefill(wa_model* m);
+// The prompt pass of group g over the call's prompts: right-aligns them to the
+// group's longest, P, runs the decoder over all P rows of every clip (self-K/V
+// into the caches at slots pad .. P - 1), leaves the last position's logits in
+// g.logits and, a scored call, the SOT-position scores; *P_out = P.
+wq4_status prefill_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st, int* P_out);
 
 // ---- wa_transcribe.cpp
 bool bad_temperatures(const float* t, int n);  // one is negative or not finite
@@ -423,5 +464,11 @@ bool bad_temperatures(const float* t, int n);  // one is negative or not finite
 wq4_status transcribe_ladder(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
                              const wa_fallback* fb, int32_t* tokens_out, int32_t* n_tokens_out,
                              const wa_scores* scores, int32_t* rung_out, void* stream);
+// wa_transcribe's argument check (wa_prompt.cpp's entries share it)
+wq4_status check_args(const wa_model* m, bool ptrs_ok, int n_batches, int max_tokens, int n_clips,
+                      const float* temps = nullptr, const int* rungs = nullptr);
+// a transcribe through the range tiers
+wq4_status transcribe_tiers(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
+                            int32_t* tokens_out, int32_t* n_tokens_out, void* stream, const wa_scores* scores);
 
 }  // namespace wa

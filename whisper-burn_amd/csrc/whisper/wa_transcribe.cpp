@@ -142,6 +142,8 @@ wq4_status run_decode(wa_model* m, const DecodeCall& call, int B, int n, int mas
     g.nb = n > 1 ? B : (int)((int64_t)B * (i + 1) / G) - g.b0;
     g.clip0 = (batch0 + g.lane) * B + g.b0;
     WA_HIP(hipStreamWaitEvent(g.st, ready, 0));
+    // the prefills of a prompted call share one set of activations: one group after another
+    if (call.prompt && i > 0) WA_HIP(hipStreamWaitEvent(g.st, gprompt[i - 1], 0));
     WA_TRY(prompt_group(m, g, call, g.st));
     WA_HIP(hipEventRecord(gprompt[i], g.st));
     WA_TRY(ensure_graph(m, g, call));
@@ -650,9 +652,8 @@ wq4_status wa::transcribe_ladder(wa_model* m, const DecodeCall& call, const floa
 
 // A transcribe through the range tiers; the scores are those of the run whose
 // tokens are returned.
-static wq4_status transcribe_tiers(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
-                                   int32_t* tokens_out, int32_t* n_tokens_out, void* stream,
-                                   const wa_scores* scores) {
+wq4_status wa::transcribe_tiers(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
+                                int32_t* tokens_out, int32_t* n_tokens_out, void* stream, const wa_scores* scores) {
   // A flagged run is retried one range tier up (wa_model::range_tier), sticky
   // for the model: its activations evidently exceed the range below.
   //   0 -> 1  the LayerNorm fold feeds the raw residual stream to the MFMAs
@@ -701,8 +702,8 @@ static wq4_status transcribe_batches(wa_model* m, const DecodeCall& call, const 
 // The transcribe entries' argument check, in one order.  ptrs_ok: no pointer
 // the entry needs is null.  temps (nullable): a ladder's temperatures, one per
 // rung (`rungs` set), or a sampled call's, one per clip.
-static wq4_status check_args(const wa_model* m, bool ptrs_ok, int n_batches, int max_tokens, int n_clips,
-                             const float* temps = nullptr, const int* rungs = nullptr) {
+wq4_status wa::check_args(const wa_model* m, bool ptrs_ok, int n_batches, int max_tokens, int n_clips,
+                          const float* temps, const int* rungs) {
   if (!m || !ptrs_ok) return fail(WQ4_EINVAL, "null argument");
   if (n_batches < 1) return fail(WQ4_EINVAL, "n_batches must be >= 1");
   if (rungs && (*rungs < 1 || *rungs > 8)) return fail(WQ4_EINVAL, "the ladder has 1 .. 8 rungs");

@@ -77,6 +77,21 @@ class LongSegment(ctypes.Structure):
                 ("tok_end", ctypes.c_int32), ("start", ctypes.c_double), ("end", ctypes.c_double)]
 
 
+class Prompt(ctypes.Structure):
+    """struct wa_prompt: host prompts [n_clips, ld] and their lengths."""
+
+    _fields_ = [("tokens", ctypes.POINTER(ctypes.c_int32)), ("n_tokens", ctypes.POINTER(ctypes.c_int32)),
+                ("ld", ctypes.c_int)]
+
+
+class LongPrompt(ctypes.Structure):
+    """struct wa_long_prompt: per-recording initial prompts and the conditioning switch."""
+
+    _fields_ = [("initial", ctypes.POINTER(ctypes.c_int32)), ("n_initial", ctypes.POINTER(ctypes.c_int32)),
+                ("ld", ctypes.c_int), ("condition_on_previous_text", ctypes.c_int),
+                ("reset_temperature", ctypes.c_float)]
+
+
 RULE_FIELDS = ("text_ok", "ts_lo", "ts_hi", "first", "last", "penult", "t_last", "pad")  # a rule record's 8 int32
 
 
@@ -214,6 +229,31 @@ def lib() -> ctypes.CDLL:
         for n in ("wa_long_mel_max", "wa_long_mel_windows", "wa_long_advance", "wa_long_round", "wa_transcribe_long",
                   "wa_long_result_streams", "wa_long_result_max_tokens", "wa_long_result_stream",
                   "wa_long_result_windows", "wa_long_result_window", "wa_long_result_segments"):
+            getattr(L, n).restype = c_int
+        pp = ctypes.POINTER(Prompt)
+        L.wa_transcribe_prompted.argtypes = [vp, vp, c_int, pp, c_int, c_int, ctypes.POINTER(Sampling), i32p, i32p, sp,
+                                             vp]
+        L.wa_transcribe_fallback_prompted.argtypes = [vp, vp, c_int, pp, c_int, c_int, ctypes.POINTER(Fallback), i32p,
+                                                      i32p, sp, i32p, vp]
+        L.wa_prompt_logits_ragged.argtypes = [vp, pp, c_int, vp, vp]
+        L.wa_prompt_check.argtypes = [pp, c_int, c_int, c_int, c_int]
+        L.wa_prompt_check.restype = c_int
+        L.wa_self_attention_pad_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, i32p, c_int, vp]
+        L.wa_self_attention_prefill_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, i32p, c_int, c_int, c_int, vp]
+        L.wa_cross_attention_prefill_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
+        L.wa_embed_pad_check.argtypes = [c_int, i32p, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, i32p,
+                                         vp, c_int, vp, vp, vp]
+        L.wa_transcribe_long_prompted.argtypes = [vp, vp, c_int, i64p, i64p, ctypes.POINTER(LongOptions),
+                                                  ctypes.POINTER(LongPrompt), ctypes.POINTER(vp), vp]
+        L.wa_long_result_prompt_len.argtypes = [vp, c_int, c_int, cip]
+        L.wa_long_prompt_window.argtypes = [i32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, i32p, c_int, cip,
+                                            cip]
+        L.wa_long_prompt_next.argtypes = [i32p, cip, cip, i32p, c_int, c_int, c_int, ctypes.c_float, c_int,
+                                          ctypes.c_float]
+        for n in ("wa_transcribe_prompted", "wa_transcribe_fallback_prompted", "wa_prompt_logits_ragged",
+                  "wa_self_attention_pad_check", "wa_self_attention_prefill_check",
+                  "wa_cross_attention_prefill_check", "wa_embed_pad_check", "wa_transcribe_long_prompted",
+                  "wa_long_result_prompt_len", "wa_long_prompt_window", "wa_long_prompt_next"):
             getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
@@ -521,6 +561,106 @@ def self_attention_check(qkv, cache_k, cache_v, Tq: int, H: int, kv_len: int, pr
     check(lib().wa_self_attention_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, Tq, H,
                                         ctx, kv_len, precision, _ptr(out)))
     return out
+
+
+def _prompt_arrays(prompts, n: Optional[int] = None, min_len: int = 1):
+    """A list of id sequences -> (tokens [n, ld] int32, n_tokens [n] int32, ld); lengths below min_len keep ld >= 1."""
+    prompts = [np.asarray(p, np.int64).reshape(-1) for p in prompts]
+    assert n is None or len(prompts) == n
+    ld = max([1] + [p.size for p in prompts])
+    tok = np.zeros((len(prompts), ld), np.int32)
+    for i, p in enumerate(prompts):
+        tok[i, :p.size] = np.clip(p, -(1 << 31), (1 << 31) - 1)
+    return tok, np.asarray([p.size for p in prompts], np.int32), ld
+
+
+def self_attention_pad_check(qkv, cache_k, cache_v, H: int, kv_len: int, pad, precision: int = wq4.PREC_F16X2):
+    """self_attention_check with Tq = 1 in the pad form of a prompted decode step
+    (wa_self_attention_pad_check): pad host int32 [B], clip b's entries are
+    cache slots [pad[b], kv_len)."""
+    torch = _torch()
+    B, _, ctx, _ = cache_k.shape
+    pad = _i32(pad)
+    assert pad.size == B
+    out = torch.empty((B, 64 * H), device=qkv.device, dtype=torch.float32)
+    check(lib().wa_self_attention_pad_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, H, ctx,
+                                            kv_len, _as(pad, ctypes.c_int32), precision, _ptr(out)))
+    return out
+
+
+def self_attention_prefill_check(qkv, cache_k, cache_v, P: int, pad, H: int, precision: int = wq4.PREC_F16X2):
+    """The prefill's self-attention (wa_self_attention_prefill_check): qkv cuda
+    f32 [B*P, 3*64H], pad host int32 [B] (clip b's rows are [pad[b], P)); caches
+    [B, H, ctx, 64], slots pad[b] .. P-1 written in place -> [B*P, 64H]."""
+    torch = _torch()
+    B, _, ctx, _ = cache_k.shape
+    pad = _i32(pad)
+    assert pad.size == B and qkv.shape[0] == B * P
+    out = torch.empty((B * P, 64 * H), device=qkv.device, dtype=torch.float32)
+    check(lib().wa_self_attention_prefill_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, P,
+                                                _as(pad, ctypes.c_int32), H, ctx, precision, _ptr(out)))
+    return out
+
+
+def cross_attention_prefill_check(q, k, v, P: int, precision: int = wq4.PREC_F16X2):
+    """The prefill's cross-attention (wa_cross_attention_prefill_check): q cuda
+    f32 [B*P, 64H], k / v head-major [B, H, T, 64] -> [B*P, 64H]."""
+    torch = _torch()
+    B, H, T, _ = k.shape
+    assert q.shape == (B * P, 64 * H) and k.is_contiguous() and v.is_contiguous()
+    out = torch.empty((B * P, 64 * H), device=q.device, dtype=torch.float32)
+    check(lib().wa_cross_attention_prefill_check(_dev(q), _ptr(q.contiguous()), _ptr(k), _ptr(v), B, P, T, H,
+                                                 precision, _ptr(out)))
+    return out
+
+
+def embed_pad_check(tokens, tok_emb, pos_emb, B: int, Tq: int, pos0: int, pad, use_state: bool = False, gamma=None,
+                    precision: int = wq4.PREC_F16X2):
+    """embed_check in the pad form (wa_embed_pad_check): pad host int32 [B],
+    clip b's rows get positions pos0 + t - pad[b]."""
+    torch = _torch()
+    V, D = tok_emb.shape
+    ctx = pos_emb.shape[0]
+    tokens = np.ascontiguousarray(tokens, np.int32)
+    pad = _i32(pad)
+    assert tokens.size == B * Tq and pad.size == B and tok_emb.is_contiguous() and pos_emb.is_contiguous()
+    R = B * Tq
+    x = torch.empty((R, D), device=tok_emb.device, dtype=torch.float32)
+    tiled = stats = None
+    if gamma is not None:
+        tiled = torch.zeros(wq4.lib().wq4_atiled_bytes(R, D, precision), device=tok_emb.device, dtype=torch.uint8)
+        stats = torch.empty((R, D // 16, 2), device=tok_emb.device, dtype=torch.float32)
+    check(lib().wa_embed_pad_check(_dev(tok_emb), _as(tokens, ctypes.c_int32), _ptr(tok_emb), V, _ptr(pos_emb), ctx, B,
+                                   Tq, D, pos0, 1 if use_state else 0, _as(pad, ctypes.c_int32),
+                                   None if gamma is None else _ptr(gamma), precision, _ptr(x),
+                                   None if gamma is None else _ptr(tiled), None if gamma is None else _ptr(stats)))
+    return x, tiled, stats
+
+
+def long_prompt_window(prev, reset: int, n_text_ctx: int, max_tokens: int, startofprev: int, lang_token: int,
+                       task_token: int) -> tuple[list[int], int]:
+    """A window's prompt and its previous-text length k (wa_long_prompt_window, host only)."""
+    prev = _i32(prev)
+    out = np.zeros(n_text_ctx + 4, np.int32)
+    n, k = ctypes.c_int(), ctypes.c_int()
+    check(lib().wa_long_prompt_window(_as(prev, ctypes.c_int32), int(prev.size), int(reset), n_text_ctx, max_tokens,
+                                      startofprev, lang_token, task_token, _as(out, ctypes.c_int32), int(out.size),
+                                      ctypes.byref(n), ctypes.byref(k)))
+    return out[:n.value].tolist(), k.value
+
+
+def long_prompt_next(prev, reset: int, tokens, ts0: int, skipped: bool, temperature: float,
+                     condition_on_previous_text: bool, reset_temperature: float = 0.5) -> tuple[list[int], int]:
+    """What a decoded window adds to a recording's previous text (wa_long_prompt_next, host only)."""
+    prev, tokens = _i32(prev), _i32(tokens)
+    buf = np.zeros(prev.size + tokens.size + 1, np.int32)
+    buf[:prev.size] = prev
+    n, r = ctypes.c_int(int(prev.size)), ctypes.c_int(int(reset))
+    check(lib().wa_long_prompt_next(_as(buf, ctypes.c_int32), ctypes.byref(n), ctypes.byref(r),
+                                    _as(tokens, ctypes.c_int32), int(tokens.size), ts0, 1 if skipped else 0,
+                                    float(temperature), 1 if condition_on_previous_text else 0,
+                                    float(reset_temperature)))
+    return buf[:n.value].tolist(), r.value
 
 
 def logits_argmax_check(hid, emb, step: int, precision: int = wq4.PREC_F16X2, want_logits: bool = True):
@@ -918,10 +1058,45 @@ class WhisperModel:
                              fallback=(temperatures, logprob_threshold, no_speech_threshold, seed, timestamps))
         return self._timestamped(clips) if timestamps else clips
 
+    def transcribe_prompted(self, mel, prompts, max_tokens: int = 224, eot_stop: bool = True, temperature=None,
+                            seed=0, timestamps: bool = False, max_initial: int = 50) -> list[dict]:
+        """transcribe under the caller's prompts (wa_transcribe_prompted):
+        prompts, one sequence of token ids per clip, of any lengths with
+        max(len) + max_tokens <= n_text_ctx -- all of it the caller's
+        (<|startofprev|> and previous text, SOT, language, task,
+        NO_TIMESTAMPS).  temperature None: the greedy pick without timestamp
+        rules; else as transcribe_sampled (0 decodes greedily; timestamps
+        selects the rules).  Per clip the dict of transcribe_scored, the scores
+        taken at the prompt's last SOT."""
+        sampling = None if temperature is None else (temperature, seed, timestamps)
+        clips = self._scored(mel, None, None, max_tokens, eot_stop, max_initial, sampling=sampling, prompts=prompts)
+        return self._timestamped(clips) if timestamps and sampling is not None else clips
+
+    def fallback_prompted(self, mel, prompts, seed, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
+                          logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
+                          max_tokens: int = 224, eot_stop: bool = True, timestamps: bool = False,
+                          max_initial: int = 50) -> list[dict]:
+        """transcribe_fallback under the caller's prompts (wa_transcribe_fallback_prompted)."""
+        clips = self._scored(mel, None, None, max_tokens, eot_stop, max_initial, prompts=prompts,
+                             fallback=(temperatures, logprob_threshold, no_speech_threshold, seed, timestamps))
+        return self._timestamped(clips) if timestamps else clips
+
+    def prompt_logits_ragged(self, prompts):
+        """After encode(): the prefill over prompts of any lengths (one id
+        sequence per encoded clip) -> last-position logits [B, n_vocab]."""
+        torch = _torch()
+        ptok, pn, pld = _prompt_arrays(prompts)
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        pr = Prompt(ptok.ctypes.data_as(i32p), pn.ctypes.data_as(i32p), pld)
+        out = torch.empty((len(prompts), self.config["n_vocab"]), device=f"cuda:{self.device}", dtype=torch.float32)
+        check(lib().wa_prompt_logits_ragged(self._h, ctypes.byref(pr), len(prompts), _ptr(out), self._stream()))
+        return out
+
     def transcribe_long(self, audio, n_samples=None, seed=0, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
                         lang_token: Optional[int] = 50259, max_tokens: int = 224, max_windows: int = 1 << 20,
-                        max_initial: int = 50) -> list[dict]:
+                        max_initial: int = 50, initial_prompts=None, condition_on_previous_text: bool = False,
+                        reset_temperature: float = 0.5) -> list[dict]:
         """Long-form transcription (wa_transcribe_long): OpenAI transcribe()'s
         loop -- the window at seek, timestamp decode with the temperature
         ladder, the silence skip, segments in absolute seconds, seek advanced
@@ -933,7 +1108,12 @@ class WhisperModel:
         threshold off.  Per recording a dict: "windows", each the dict of
         transcribe_fallback's clip plus seek, size, advance (mel frames) and
         skipped; "segments", (start_s, end_s, tokens) in seconds of the
-        recording; "truncated", whether max_windows ended it early."""
+        recording; "truncated", whether max_windows ended it early.
+        initial_prompts (one id sequence per recording, possibly empty) and
+        condition_on_previous_text (OpenAI's default is True; here the caller
+        chooses) run wa_transcribe_long_prompted: every window is prompted with
+        the recording's previous text, and its dict gains "prompt_len".  The
+        defaults are wa_transcribe_long."""
         torch = _torch()
         if isinstance(audio, (list, tuple)):
             assert n_samples is None and all(a.dim() == 1 for a in audio)
@@ -960,15 +1140,24 @@ class WhisperModel:
                           nan if no_speech_threshold is None else float(no_speech_threshold),
                           _as(sd, ctypes.c_uint64))
         h = ctypes.c_void_p(None)
-        check(lib().wa_transcribe_long(self._h, _ptr(buf), S, _as(off, ctypes.c_int64), _as(n, ctypes.c_int64),
-                                       ctypes.byref(opt), ctypes.byref(h), self._stream()))
+        prompted = initial_prompts is not None or condition_on_previous_text
+        if prompted:
+            itok, inn, ild = _prompt_arrays(initial_prompts if initial_prompts is not None else [[]] * S, S)
+            lp = LongPrompt(_as(itok, ctypes.c_int32), _as(inn, ctypes.c_int32), ild,
+                            1 if condition_on_previous_text else 0, float(reset_temperature))
+            check(lib().wa_transcribe_long_prompted(self._h, _ptr(buf), S, _as(off, ctypes.c_int64),
+                                                    _as(n, ctypes.c_int64), ctypes.byref(opt), ctypes.byref(lp),
+                                                    ctypes.byref(h), self._stream()))
+        else:
+            check(lib().wa_transcribe_long(self._h, _ptr(buf), S, _as(off, ctypes.c_int64), _as(n, ctypes.c_int64),
+                                           ctypes.byref(opt), ctypes.byref(h), self._stream()))
         try:
-            return [self._long_stream(h, r, max_tokens) for r in range(S)]
+            return [self._long_stream(h, r, max_tokens, prompted) for r in range(S)]
         finally:
             lib().wa_long_result_free(h)
 
     @staticmethod
-    def _long_stream(h, r: int, max_tokens: int) -> dict:
+    def _long_stream(h, r: int, max_tokens: int, prompted: bool = False) -> dict:
         L = lib()
         nw, tr, nsg = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(L.wa_long_result_stream(h, r, ctypes.byref(nw), ctypes.byref(tr), ctypes.byref(nsg)))
@@ -985,13 +1174,17 @@ class WhisperModel:
             clip = _scored_clip(toks, nt.value, lp, w.no_speech_prob, w.lang_token, w.lang_prob)
             clip.update(avg_logprob=float(w.avg_logprob), rung=int(w.rung), temperature=float(w.temperature),
                         seek=int(w.seek), size=int(w.size), advance=int(w.advance), skipped=bool(w.skipped))
+            if prompted:
+                k = ctypes.c_int()
+                check(L.wa_long_result_prompt_len(h, r, i, ctypes.byref(k)))
+                clip["prompt_len"] = k.value
             windows.append(clip)
         segments = [(float(s.start), float(s.end), windows[s.window]["tokens"][s.tok_begin:s.tok_end])
                     for s in segs[:nsg.value]]
         return {"windows": windows, "segments": segments, "truncated": bool(tr.value)}
 
     def _scored(self, mels, NB: Optional[int], lang_token, max_tokens: int, eot_stop: bool,
-                max_initial: Optional[int] = None, sampling=None, fallback=None):
+                max_initial: Optional[int] = None, sampling=None, fallback=None, prompts=None):
         torch = _torch()
         mels = mels.contiguous()
         assert mels.dtype == torch.float32 and mels.is_cuda
@@ -1006,7 +1199,34 @@ class WhisperModel:
                     lpr.ctypes.data_as(f32p))
         lang = -1 if lang_token is None else int(lang_token)
         rung = None
-        if fallback is not None:
+        if prompts is not None:  # the prompted entries: the prompt in the language token's place
+            assert NB is None
+            ptok, pn, pld = _prompt_arrays(prompts, n)
+            pr = Prompt(ptok.ctypes.data_as(i32p), pn.ctypes.data_as(i32p), pld)
+        if prompts is not None and fallback is not None:
+            temps, lp_thr, ns_thr, seed, ts = fallback
+            tl = np.ascontiguousarray(np.asarray(temps, np.float32).reshape(-1))
+            _, sd = _sampling_arrays(0.0, seed, n)
+            nan = float("nan")
+            fb = Fallback(tl.ctypes.data_as(f32p), int(tl.size), nan if lp_thr is None else float(lp_thr),
+                          nan if ns_thr is None else float(ns_thr), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                          1 if ts else 0, int(max_initial))
+            rung = np.zeros(n, np.int32)
+            check(lib().wa_transcribe_fallback_prompted(self._h, _ptr(mels), B, ctypes.byref(pr), max_tokens,
+                                                        1 if eot_stop else 0, ctypes.byref(fb),
+                                                        toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p),
+                                                        ctypes.byref(sc), rung.ctypes.data_as(i32p), self._stream()))
+        elif prompts is not None:
+            sm = None
+            if sampling is not None:
+                temperature, seed, ts = sampling
+                t, sd = _sampling_arrays(temperature, seed, n)
+                sm = ctypes.byref(Sampling(t.ctypes.data_as(f32p), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                                           1 if ts else 0, int(max_initial)))
+            check(lib().wa_transcribe_prompted(self._h, _ptr(mels), B, ctypes.byref(pr), max_tokens,
+                                               1 if eot_stop else 0, sm, toks.ctypes.data_as(i32p),
+                                               nt.ctypes.data_as(i32p), ctypes.byref(sc), self._stream()))
+        elif fallback is not None:
             temps, lp_thr, ns_thr, seed, ts = fallback
             tl = np.ascontiguousarray(np.asarray(temps, np.float32).reshape(-1))
             _, sd = _sampling_arrays(0.0, seed, n)
