@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import oracle
+import q4_shapes
 import wq4
 
 pytestmark = pytest.mark.gpu
@@ -48,13 +49,18 @@ def to_dev(torch, a, shape):
     return torch.from_numpy(np.ascontiguousarray(a, np.float32).reshape(shape)).to("cuda:0")
 
 
-def assert_q4_close(y, x2d, deq2d, prec=wq4.PREC_F16X2, bias=None, what=""):
+def assert_q4_close(y, x2d, deq2d, prec=wq4.PREC_F16X2, bias=None, what="", residual=None):
+    """residual [m, n]: y = residual + (x W^T + bias) (WQ4_EPI_RESIDUAL), one
+    more f32 addition and so one more 2^-24 rounding of its own result."""
     truth, mag = oracle.matmul_f64(x2d, deq2d)
     if bias is not None:
         truth = truth + np.asarray(bias, np.float64)[None, :]
     wabs = np.abs(np.asarray(deq2d, np.float64)).sum(axis=1)[None, :]
     rel, ab = TOL[prec]
     bound = rel * mag + ab * wabs + 1e-30 + (0 if bias is None else 2**-24 * np.abs(truth))
+    if residual is not None:
+        truth = truth + np.asarray(residual, np.float64).reshape(truth.shape)
+        bound = bound + 2**-24 * np.abs(truth)
     err = np.abs(np.asarray(y, np.float64).reshape(truth.shape) - truth)
     worst = float(np.max(err / bound))
     assert worst <= 1.0, f"{what}: max err/bound = {worst:.3g} (max err {err.max():.3g})"
@@ -834,15 +840,7 @@ def test_enc_epilogue_past_2gib(torch, flags):
 
 
 # ------------------------------- encoder GEMM: LDS-DMA ring kernel (wq4_enc.hip) --
-@pytest.mark.parametrize("m,n,k,flags,prec", [(1500, 1280, 1280, 0, 0), (3000, 3840, 1280, 0, 0), (700, 5120, 1280, 5, 0),
-                                              (300, 1280, 5120, 2, 0), (2049, 1280, 1280, 1, 0), (16000, 1280, 1280, 2, 0),
-                                              (4500, 5120, 1280, 5, 0), (200, 96, 160, 0, 0), (1000, 1312, 1280, 4, 0),
-                                              (2049, 1280, 1280, 4, 0), (1500, 1280, 5120, 3, 0), (2000, 5120, 1280, 5, 1),
-                                              (300, 1312, 160, 4, 1),
-                                              # K loop lengths for the wide kernel's peeled first block pair,
-                                              # three-pair trips and 0-3 trailing pairs (nbp = K / 64: 1, 4, 5, 6, 7)
-                                              (600, 1280, 64, 1, 0), (500, 1280, 256, 0, 0), (900, 1280, 320, 2, 0),
-                                              (400, 1280, 384, 0, 1), (700, 1280, 448, 4, 0)])
+@pytest.mark.parametrize("m,n,k,flags,prec", q4_shapes.ENC_BIT_IDENTICAL)  # shared with test_q4_routing.py (CPU)
 def test_enc_kernel_bit_identical(torch, m, n, k, flags, prec):
     """The encoder-size GEMM kernels -- the ring kernel (its geometries: 256 x
     256 with 8 waves, 64 x 128 and 32 x 256 with 4) and the 8-wave wide
@@ -850,7 +848,9 @@ def test_enc_kernel_bit_identical(torch, m, n, k, flags, prec):
     exactly: the same per-block MFMA chain and scale FMA order, only the
     memory pipeline differs.  flags: 1 GELU, 2 residual, 4 A-tiled output
     (then compared fragment for fragment, padding included).  prec 1 (f16
-    operands): the ring kernel is f16x2-only, so the tile and wide kernels."""
+    operands): the ring kernel is f16x2-only, so the tile and wide kernels.
+    Before each launch the routing is asserted (wq4_gemm_kernel_name against
+    q4_shapes.expected_kernel): no mode silently runs another kernel."""
     import ctypes
 
     rng = np.random.default_rng(m + n + k + flags)
@@ -871,6 +871,9 @@ def test_enc_kernel_bit_identical(torch, m, n, k, flags, prec):
     try:
         for mode in modes:
             assert L.wq4_debug_set_enc_kernel(mode) >= 0
+            wq4.set_kernel_policy(1)
+            wq4.set_precision(prec)
+            assert wq4.gemm_kernel_name(n, k, m) == q4_shapes.expected_kernel(mode, m, n, prec), f"mode {mode}"
             y = res.clone() if flags & 2 else torch.full((m, n), 7.0, device="cuda:0")
             ot = torch.full((L.wq4_atiled_bytes(m, n, prec),), 0x5A, dtype=torch.uint8, device="cuda:0") if tiled else None
             wq4.check(L.wq4_gemm_tiled(t.handle, p(b), p(at), p(y) if flags & 2 else None, None if tiled else p(y),
