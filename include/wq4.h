@@ -285,6 +285,22 @@ wq4_status wq4_set_kernel_policy(int policy);
  * "q4_gemm_decode_kernel", "q4_gemm_enc_kernel", "q4_gemm_prefill_kernel";
  * "" for a shape no GEMM accepts).  Host only (bench.py's roofline label). */
 const char* wq4_gemm_kernel_name(int64_t n, int64_t k, int64_t rows);
+/* The launch plan of that GEMM, from the launchers' own planning functions.
+ * weight_type: 0 = Q4_0, 1 = f16 weights.  Returns out[0], the kernel id:
+ * 0 = a shape no GEMM accepts (out all zeros);
+ * 1 = the tile kernel family, also where the decode kernel was asked for and
+ *     does not take the shape; out[1] = 0 the prefill tile kernel, 2-4 the
+ *     ring kernel's geometry, 5 the wide kernel;
+ * 2 = the decode kernel: out[1] waves per workgroup (8 or 4), out[2] the
+ *     kernel instance's block pairs per wave, out[3] K slices per n-tile,
+ *     out[4] block pairs per wave in use (chunk), out[5] m-tile launches on
+ *     the one workspace;
+ * 3 = the decode-step kernel: out[3] K slices, out[6] 16-column subtiles per
+ *     workgroup (1, 2, 4), out[7] 16-row tiles (1, 2).
+ * Entries not named are 0.  The report is by shape: a tensor made without
+ * the decode-step layout (WQ4_TENSOR_NO_DECODE_STEP; f16 weights out of its
+ * range) never runs kernel 3.  Host only. */
+int wq4_gemm_plan(int64_t n, int64_t k, int64_t rows, int weight_type, int out[8]);
 
 /* ---- host-only diagnostics (no GPU needed) ---------------------------- */
 /* Sizes of the repacked nibble / scale / column-scale arrays for [N, K]. */

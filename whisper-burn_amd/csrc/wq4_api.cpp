@@ -255,18 +255,47 @@ wq4_status wq4_set_kernel_policy(int policy) {
   return WQ4_OK;
 }
 
-const char* wq4_gemm_kernel_name(int64_t n, int64_t k, int64_t rows) {
-  if (n < 1 || k < 32 || k % 32 != 0 || rows < 1) return "";
+int wq4_gemm_plan(int64_t n, int64_t k, int64_t rows, int weight_type, int out[8]) {
+  if (!out) return 0;
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (n < 1 || k < 32 || k % 32 != 0 || rows < 1 || rows > (1 << 24) || weight_type < 0 || weight_type > 1)
+    return 0;
   const wq4::Q4Geom g = wq4::make_geom(n, k);
   // the decode-step layout exists for K % 128 == 0, N % 16 == 0 (upload)
   const bool skinny = k % 128 == 0 && n % 16 == 0 && wq4::skinny_supported(g, (int)rows);
   const int pol = g_policy.load();
-  int kern = pol != 0 ? (pol == 3 && !skinny ? 2 : pol) : skinny ? 3 : use_decode(rows) ? 2 : 1;
-  switch (kern) {
+  const int kern = pol != 0 ? (pol == 3 && !skinny ? 2 : pol) : skinny ? 3 : use_decode(rows) ? 2 : 1;
+  if (kern == 3) {
+    out[0] = 3;
+    out[3] = wq4::skinny_ks(g);
+    out[6] = wq4::skinny_nt(g, (int)rows);
+    out[7] = (int)((rows + 15) / 16);
+    return 3;
+  }
+  wq4::DecodePlan p;
+  if (kern == 2 && wq4::decode_plan_of(g, (int)rows, &p)) {
+    const int mreal = (int)((rows + 31) / 32);
+    out[0] = 2;
+    out[1] = p.w;
+    out[2] = p.per;
+    out[3] = p.ks;
+    out[4] = p.chunk;
+    out[5] = p.w == 8 ? mreal : (mreal + 1) / 2;
+    return 2;
+  }
+  out[0] = 1;  // the tile kernel family, also where the decode kernel does not take the shape
+  out[1] = wq4::enc_gemm_pick(g, (int)rows, 0, g_prec.load() == WQ4_PREC_F16X2 ? 2 : 1, weight_type);
+  return 1;
+}
+
+const char* wq4_gemm_kernel_name(int64_t n, int64_t k, int64_t rows) {
+  int plan[8];
+  switch (wq4_gemm_plan(n, k, rows, 0, plan)) {
+    case 0: return "";
     case 3: return "skinny_gemm_kernel";
     case 2: return "q4_gemm_decode_kernel";
     default:
-      switch (wq4::enc_gemm_pick(g, (int)rows, 0, g_prec.load() == WQ4_PREC_F16X2 ? 2 : 1, 0)) {
+      switch (plan[1]) {
         case 0: return "q4_gemm_prefill_kernel";
         case 5: return "q4_gemm_wide_kernel";
         default: return "q4_gemm_enc_kernel";

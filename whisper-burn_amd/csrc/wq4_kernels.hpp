@@ -53,6 +53,11 @@ constexpr int kWeightsQ4 = 0, kWeightsF16 = 1;
 // Whether launch_q4_gemm can build the A operand by LayerNorm-on-load
 // (EpiArgs::lnx) for this weight and row count: 8-wave decode plans.
 bool decode_ln_supported(const Q4Geom& g, int rows);
+// Whether launch_q4_gemm with a workspace runs the decode kernel for this
+// weight and row count (else: the tile kernel family), and the plan it runs
+// (plan may be null).  8-wave plans launch once per 32-row m-tile, 4-wave
+// plans once per two.
+bool decode_plan_of(const Q4Geom& g, int rows, DecodePlan* plan);
 hipError_t launch_q4_gemm(const Q4Geom& g, const uint8_t* nib, const uint32_t* sc, const float* colscale,
                           const _Float16* at, int rows, const EpiArgs& e, int epi_mode, int ns, const DecodeWs* ws,
                           hipStream_t st, int wtype);
@@ -83,6 +88,11 @@ inline size_t skinny_f16_bytes(const Q4Geom& g) { return (size_t)(g.np / 16) * g
 void repack_q4_skinny(const uint8_t* raw, const Q4Geom& g, uint32_t* q16, uint16_t* d16);
 void repack_f16_skinny(const uint16_t* w, const Q4Geom& g, uint16_t* f16s);
 bool skinny_supported(const Q4Geom& g, int rows);
+// Its launch plan: K slices per column tile (1, 2, 4, 8; 0 = unsupported K)
+// and 16-column subtiles per workgroup (1, 2, 4); the grid is np / (16 nt) x
+// ceil(rows / 16) row tiles x ks.
+int skinny_ks(const Q4Geom& g);
+int skinny_nt(const Q4Geom& g, int rows);
 constexpr int kSkinnyMaxLnTiles = 80;  // LayerNorm-fold consumer: K / 16 tile statistics per row
 // ws: the stream's split-K workspace (partials + arrival counters) for the
 // K splits of large K (fc2).

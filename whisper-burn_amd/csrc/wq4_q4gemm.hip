@@ -1062,6 +1062,16 @@ bool decode_ln_supported(const Q4Geom& g, int rows) {
   return rows >= 1 && mreal0 <= kDecodeMaxMTiles && p.w == 8 && p.per <= kDecodeMaxPer8;
 }
 
+// Whether launch_gemm_t runs the decode kernel for this weight and row count
+// when handed the workspace (else it falls back to the tile kernel family),
+// and the plan it launches: the launcher's own acceptance condition.
+bool decode_plan_of(const Q4Geom& g, int rows, DecodePlan* plan) {
+  const int mreal0 = (int)((rows + kMTile - 1) / kMTile);
+  const DecodePlan p = plan_decode(g.ntiles, g.nbp, 2);
+  if (plan) *plan = p;
+  return rows >= 1 && mreal0 <= kDecodeMaxMTiles && p.per <= (p.w == 8 ? kDecodeMaxPer8 : kDecodeMaxPer);
+}
+
 hipError_t launch_q4_gemm(const Q4Geom& g, const uint8_t* nib, const uint32_t* sc, const float* colscale,
                           const _Float16* at, int rows, const EpiArgs& e, int epi_mode, int ns, const DecodeWs* ws,
                           hipStream_t st, int wtype) {

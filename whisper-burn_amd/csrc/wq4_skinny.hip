@@ -422,7 +422,7 @@ __global__ __launch_bounds__(64 * kSkW) void skinny_gemm_kernel(const uint32_t* 
 // K split over workgroups: the smallest of 1, 2, 4, 8 that divides the block
 // count and leaves <= kSkBpw blocks per wave (a function of K only, so the
 // per-row arithmetic never depends on M); 0 = unsupported.
-static int skinny_ks(const Q4Geom& g) {
+int skinny_ks(const Q4Geom& g) {
   for (int ks = 1; ks <= 8; ks *= 2)
     if (g.kb % ks == 0 && (g.kb / ks + kSkW - 1) / kSkW <= kSkBpw) return ks;
   return 0;
@@ -431,7 +431,7 @@ static int skinny_ks(const Q4Geom& g) {
 // 16-column subtiles per workgroup: the fewest (1, 2, 4) that keep the grid
 // within one workgroup per CU.  Only the work split changes with it, never
 // an output's arithmetic.
-static int skinny_nt(const Q4Geom& g, int rows) {
+int skinny_nt(const Q4Geom& g, int rows) {
   const int64_t per = (int64_t)skinny_ks(g) * ((rows + 15) / 16);
   for (int nt = 1; nt < 4; nt *= 2)
     if (g.np / (16 * nt) * per <= 256) return nt;

@@ -55,6 +55,8 @@ def _declare(L: ctypes.CDLL) -> None:
     L.wq4_set_kernel_policy.argtypes = [c_int]
     L.wq4_gemm_kernel_name.argtypes = [c_i64, c_i64, c_i64]
     L.wq4_gemm_kernel_name.restype = ctypes.c_char_p
+    L.wq4_gemm_plan.argtypes = [c_i64, c_i64, c_i64, c_int, ctypes.POINTER(c_int)]
+    L.wq4_gemm_plan.restype = c_int
     L.wq4_tensor_create.argtypes = [c_int, u8p, c_sz, c_i64, c_i64, ctypes.POINTER(vp)]
     L.wq4_tensor_destroy.argtypes = [vp]
     L.wq4_tensor_destroy.restype = None
@@ -169,6 +171,23 @@ def gemm_kernel_name(n: int, k: int, rows: int) -> str:
     """The kernel a Q4_0 GEMM of `rows` rows over [n, k] weights runs under the
     current policy (host only; include/wq4.h wq4_gemm_kernel_name)."""
     return lib().wq4_gemm_kernel_name(n, k, rows).decode()
+
+
+def gemm_plan(n: int, k: int, rows: int, weight_type: int = 0) -> dict:
+    """The launch plan of that GEMM (host only; include/wq4.h wq4_gemm_plan):
+    {"kernel": 0} for a shape no GEMM accepts; {"kernel": 1, "geo"} the tile
+    kernel family; {"kernel": 2, "w", "per", "ks", "chunk", "launches"} the
+    decode kernel; {"kernel": 3, "ks", "nt", "row_tiles"} the decode-step
+    kernel.  weight_type: 0 = Q4_0, 1 = f16."""
+    o = (ctypes.c_int * 8)()
+    kern = lib().wq4_gemm_plan(n, k, rows, weight_type, o)
+    if kern == 1:
+        return {"kernel": 1, "geo": o[1]}
+    if kern == 2:
+        return {"kernel": 2, "w": o[1], "per": o[2], "ks": o[3], "chunk": o[4], "launches": o[5]}
+    if kern == 3:
+        return {"kernel": 3, "ks": o[3], "nt": o[6], "row_tiles": o[7]}
+    return {"kernel": 0}
 
 
 def _u8p(a: np.ndarray):
