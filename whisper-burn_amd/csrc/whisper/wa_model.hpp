@@ -1,6 +1,7 @@
 // wa_model.hpp -- internal: the Whisper model runtime's state (struct
 // wa_model) and what its translation units (wa_weights, wa_forward,
-// wa_transcribe, wa_long, wa_api, wa_checks .cpp) need from one another.
+// wa_transcribe, wa_long, wa_prompt, wa_align, wa_api, wa_checks .cpp) need
+// from one another.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -12,6 +13,7 @@
 
 #include "../../../include/whisper_amd.h"
 #include "../../../include/wq4.h"
+#include "wa_align.hpp"
 #include "wa_gguf.hpp"
 #include "wa_kernels.hpp"
 #include "wa_pick.hpp"
@@ -216,6 +218,11 @@ struct DecodeCall {
   const int* trace_ids = nullptr;
   float* trace_out = nullptr;
   int trace_s1 = 0, trace_k = 0;
+  // alignment calls (wa_align; false otherwise): the prefill of `prompt` also
+  // leaves the head mean of the filtered cross-attention weights in the
+  // model's alignment buffers (wa_model::Align; the group's F uploaded by the
+  // entry) and stops there -- no logits, no scores
+  bool align = false;
 
   DecodeCall() = default;
   DecodeCall(int lang, int max_tok, int eot, bool score_, bool ts_ = false, int max_initial = 50, bool sample_ = false)
@@ -355,6 +362,22 @@ struct wa_model {
     int* tok = nullptr;
     float *xk = nullptr, *xv = nullptr;
   } pf;
+  // Token alignment (wa_align.cpp; allocated by the first wa_align,
+  // ensure_align): w, the weights of one pass of kAlignHeadsPerPass heads
+  // [pass head][bmax][n_text_ctx][fld] f32; msum, their filtered head mean
+  // [bmax][n_text_ctx][fld] f32; the DTW's trace bytes [bmax][n_text_ctx]
+  // [n_audio_ctx + 1]; per-clip F, first matrix row, N, the heads of a pass and
+  // the jump frames [bmax][n_text_ctx].  heads: the (layer, head) pairs in the
+  // caller's order (empty: every head of the upper half of the layers).
+  struct Align {
+    bool ok = false;
+    int fld = 0;
+    float *w = nullptr, *msum = nullptr;
+    uint8_t* trace = nullptr;
+    int *F = nullptr, *row0 = nullptr, *N = nullptr, *heads = nullptr, *jump = nullptr;
+    std::vector<std::pair<int, int>> pairs;
+    float timings[4] = {0, 0, 0, 0};  // encoder, prefill with capture, DTW, total (ms) of the last wa_align
+  } al;
   float timings[5] = {0, 0, 0, 0, 0};
   // every group's score / timestamp / sampling buffers are allocated
   // (prepare_call: by the first call in that mode, all or nothing)
@@ -456,6 +479,13 @@ wq4_status ensure_prefill(wa_model* m);
 // into the caches at slots pad .. P - 1), leaves the last position's logits in
 // g.logits and, a scored call, the SOT-position scores; *P_out = P.
 wq4_status prefill_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st, int* P_out);
+
+// ---- wa_align.cpp
+// The capture of an alignment call after layer li's cq GEMM (prefill_group):
+// weights + filter of the layer's alignment heads over pf.q and the layer's
+// head-major K, kAlignHeadsPerPass heads at a time.  *done: no later layer has
+// alignment heads.
+wq4_status align_layer(wa_model* m, DecGroup& g, int li, const float* xk, int P, hipStream_t st, bool* done);
 
 // ---- wa_transcribe.cpp
 bool bad_temperatures(const float* t, int n);  // one is negative or not finite

@@ -214,6 +214,11 @@ wq4_status prefill_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipSt
       xk = pf.xk;
       xv = pf.xv;
     }
+    if (call.align) {
+      bool done = false;
+      WA_TRY(align_layer(m, g, (int)li, xk, P, st, &done));
+      if (done) break;
+    }
     WA_HIP(launch_prefill_cross_attention(pf.q, xk, xv, B, P, T, H, pf.atd, m->ns, st, a32));
     WA_TRY(resid_gemm(L.cout, L.cout_b, pf.atd, a32));
     if (m->abi_ffn()) {
@@ -225,6 +230,8 @@ wq4_status prefill_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipSt
     WA_TRY(ln_gemm(L.fc1, L.fc1_b, L.ln3_w, L.ln3_b, nullptr, pf.atf, WQ4_EPI_GELU | WQ4_EPI_TILED_OUT));
     WA_TRY(resid_gemm(L.fc2, L.fc2_b, pf.atf, nullptr));
   }
+  *P_out = P;
+  if (call.align) return WQ4_OK;  // the capture is all an alignment call takes from the pass
   // final LN; the logits of every clip's last row (right-aligned: row P - 1)
   WA_WQ4(wq4_layernorm(pf.x, m->dln_w, m->dln_b, rows, D, WQ4_PREC_F16X2, nullptr, pf.hid, st));
   WA_HIP(launch_logits(pf.hid + (size_t)(P - 1) * D, B, D, (int64_t)P * D, m->tok_emb, V, g.logits, st));
@@ -243,7 +250,6 @@ wq4_status prefill_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipSt
     for (int b = 0; b < B; ++b)
       if (sot_row[b] < 0) WA_HIP(hipMemcpyAsync(g.no_speech + b, &nan, 4, hipMemcpyHostToDevice, st));
   }
-  *P_out = P;
   return WQ4_OK;
 }
 

@@ -255,6 +255,19 @@ def lib() -> ctypes.CDLL:
                   "wa_cross_attention_prefill_check", "wa_embed_pad_check", "wa_transcribe_long_prompted",
                   "wa_long_result_prompt_len", "wa_long_prompt_window", "wa_long_prompt_next"):
             getattr(L, n).restype = c_int
+        L.wa_model_set_alignment_heads.argtypes = [vp, i32p, c_int]
+        L.wa_align.argtypes = [vp, vp, c_int, pp, i32p, i32p, i32p, i32p, vp, vp]
+        L.wa_last_align_timings.argtypes = [vp, f32p]
+        L.wa_align_words.argtypes = [i32p, c_int, i32p, c_int, f32p, f32p]
+        L.wa_align_matrix_check.argtypes = [c_int, vp, vp, c_int, c_int, i32p, c_int, c_int, i32p, c_int, i32p, c_int,
+                                            c_int, vp]
+        L.wa_dtw_check.argtypes = [c_int, vp, c_int, c_int, c_int, i32p, i32p, vp, vp]
+        L.wa_alignment_heads_check.argtypes = [i32p, c_int, c_int, c_int]
+        L.wa_align_check.argtypes = [pp, c_int, i32p, i32p, c_int, c_int, c_int]
+        for n in ("wa_model_set_alignment_heads", "wa_align", "wa_last_align_timings", "wa_align_words",
+                  "wa_alignment_heads_check", "wa_align_check",
+                  "wa_align_matrix_check", "wa_dtw_check"):
+            getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
                   "wa_last_pipeline_stats", "wa_last_timings", "wa_encode",
@@ -612,6 +625,51 @@ def cross_attention_prefill_check(q, k, v, P: int, precision: int = wq4.PREC_F16
     check(lib().wa_cross_attention_prefill_check(_dev(q), _ptr(q.contiguous()), _ptr(k), _ptr(v), B, P, T, H,
                                                  precision, _ptr(out)))
     return out
+
+
+def align_words(jump, word_lens):
+    """Token jump frames -> word times (wa_align_words, host only): jump the N
+    frames of a clip (the last row is EOT), word_lens the words' token counts,
+    summing to N - 1 -> (start_s, end_s) f32 [len(word_lens)]."""
+    jump, wl = _i32(jump), _i32(word_lens)
+    start, end = np.zeros(wl.size, np.float32), np.zeros(wl.size, np.float32)
+    check(lib().wa_align_words(_as(jump, ctypes.c_int32), jump.size, _as(wl, ctypes.c_int32), wl.size,
+                               _as(start, ctypes.c_float), _as(end, ctypes.c_float)))
+    return start, end
+
+
+def align_matrix_check(q, k, P: int, pad, heads, F, first_row: int = 0, precision: int = wq4.PREC_F16X2):
+    """The alignment's weights and filter kernels (wa_align_matrix_check): q cuda
+    f32 [B*P, 64H], k head-major [B, H, T, 64], pad / F host [B], heads the
+    layer's alignment heads -> cuda f32 [B, P, T]: row i of clip b is M of its
+    position first_row + i, zero past its N rows and F frames."""
+    torch = _torch()
+    B, H, T, _ = k.shape
+    pad, heads, F = _i32(pad), _i32(heads), _i32(F)
+    assert q.shape == (B * P, 64 * H) and k.is_contiguous() and pad.size == B and F.size == B
+    out = torch.empty((B, P, T), device=q.device, dtype=torch.float32)
+    check(lib().wa_align_matrix_check(_dev(q), _ptr(q.contiguous()), _ptr(k), B, P, _as(pad, ctypes.c_int32), T, H,
+                                      _as(heads, ctypes.c_int32), heads.size, _as(F, ctypes.c_int32), first_row,
+                                      precision, _ptr(out)))
+    return out
+
+
+def dtw_check(x, N, F, jump=None, want_trace: bool = True):
+    """The alignment's DTW kernel (wa_dtw_check): x cuda f32 [B, N_ld, F_ld]
+    costs, N / F host [B] -> (jump cuda int32 [B, N_ld], entries < N[b] written,
+    trace cuda uint8 [B, N_ld + 1, F_ld + 1] or None).  jump: a cuda int32
+    buffer of at least B * N_ld entries to write into."""
+    torch = _torch()
+    B, N_ld, F_ld = x.shape
+    N, F = _i32(N), _i32(F)
+    assert x.is_contiguous() and x.dtype == torch.float32 and N.size == B and F.size == B
+    if jump is None:
+        jump = torch.full((B, N_ld), -1, device=x.device, dtype=torch.int32)
+    assert jump.dtype == torch.int32 and jump.is_contiguous() and jump.numel() >= B * N_ld
+    trace = torch.full((B, N_ld + 1, F_ld + 1), 255, device=x.device, dtype=torch.uint8) if want_trace else None
+    check(lib().wa_dtw_check(_dev(x), _ptr(x), B, N_ld, F_ld, _as(N, ctypes.c_int32), _as(F, ctypes.c_int32),
+                             _ptr(jump), None if trace is None else _ptr(trace)))
+    return jump, trace
 
 
 def embed_pad_check(tokens, tok_emb, pos_emb, B: int, Tq: int, pos0: int, pad, use_state: bool = False, gamma=None,
@@ -1091,6 +1149,55 @@ class WhisperModel:
         out = torch.empty((len(prompts), self.config["n_vocab"]), device=f"cuda:{self.device}", dtype=torch.float32)
         check(lib().wa_prompt_logits_ragged(self._h, ctypes.byref(pr), len(prompts), _ptr(out), self._stream()))
         return out
+
+    def set_alignment_heads(self, pairs) -> None:
+        """The (layer, head) pairs align() averages (wa_model_set_alignment_heads);
+        an empty list restores the default, every head of the upper half of
+        the decoder layers."""
+        a = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        check(lib().wa_model_set_alignment_heads(self._h, _as(a, ctypes.c_int32), a.shape[0]))
+
+    def align(self, mel, tokens, first_row=3, n_frames=3000, return_matrix: bool = False) -> list[dict]:
+        """Token-level times of finished id sequences (wa_align, OpenAI's
+        find_alignment): mel cuda f32 [B, n_mels, 3000]; tokens one whole id
+        sequence per clip (SOT, language, task, NO_TIMESTAMPS, text ..., EOT);
+        first_row (3 for that layout) and n_frames (the clip's content mel
+        frames) one value or one per clip.  Per clip a dict: jump int32 [N], the
+        frame at which token tokens[first_row + 1 + i] starts; start_s [N] =
+        jump / 50; end_s [N - 1] = the next token's start (the last row, EOT,
+        has none); matrix (return_matrix) cuda f32 [N, n_frames // 2], the head
+        mean of the filtered attention weights the path was found in."""
+        torch = _torch()
+        mel = mel.contiguous()
+        assert mel.dtype == torch.float32 and mel.is_cuda
+        B = mel.shape[0]
+        ptok, pn, pld = _prompt_arrays(tokens, B)
+        fr = np.ascontiguousarray(np.broadcast_to(np.asarray(first_row, np.int32), (B,)))
+        nf = np.ascontiguousarray(np.broadcast_to(np.asarray(n_frames, np.int32), (B,)))
+        i32p = ctypes.POINTER(ctypes.c_int32)
+        pr = Prompt(ptok.ctypes.data_as(i32p), pn.ctypes.data_as(i32p), pld)
+        jump, rows = np.zeros((B, pld), np.int32), np.zeros(B, np.int32)
+        mat = None
+        if return_matrix:
+            mat = torch.empty((B, pld, self.config["n_audio_ctx"]), device=mel.device, dtype=torch.float32)
+        check(lib().wa_align(self._h, ctypes.c_void_p(mel.data_ptr()), B, ctypes.byref(pr), fr.ctypes.data_as(i32p),
+                             nf.ctypes.data_as(i32p), jump.ctypes.data_as(i32p), rows.ctypes.data_as(i32p),
+                             None if mat is None else _ptr(mat), self._stream()))
+        out = []
+        for b in range(B):
+            j = jump[b, :rows[b]].copy()
+            t = j.astype(np.float32) / np.float32(50.0)
+            clip = dict(jump=j, start_s=t, end_s=t[1:].copy())
+            if mat is not None:
+                clip["matrix"] = mat[b, :rows[b], :nf[b] // 2]
+            out.append(clip)
+        return out
+
+    def align_timings(self) -> dict:
+        """Device times (ms) of the last align(): encoder, prefill with the capture, DTW, total."""
+        t = (ctypes.c_float * 4)()
+        check(lib().wa_last_align_timings(self._h, t))
+        return dict(zip(("encoder_ms", "prefill_ms", "dtw_ms", "total_ms"), [float(v) for v in t]))
 
     def transcribe_long(self, audio, n_samples=None, seed=0, temperatures=(0.0, 0.2, 0.4, 0.6, 0.8, 1.0),
                         logprob_threshold: Optional[float] = -1.0, no_speech_threshold: Optional[float] = 0.6,
