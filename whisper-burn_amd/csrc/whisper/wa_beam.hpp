@@ -1,0 +1,64 @@
+// wa_beam.hpp -- launchers of the beam-search kernels (wa_beam.hip, and the
+// ancestor-table self-attention beside the kernel it mirrors in
+// wa_kernels.hip).  Semantics: include/whisper_amd.h, "Beam search".
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+#include "wa_kernels.hpp"
+
+namespace wa {
+
+constexpr int kBeamMaxK = 8;      // beams per clip
+constexpr int kBeamMaxCand = 16;  // finished sequences kept per clip
+constexpr int kBeamMaxTop = kBeamMaxK + 1;
+
+// Per-row log-softmax and top-kp (kp = K + 1 <= 9) of stored logit rows
+// [rows][V] f32 (row stride ld): one workgroup per row, one pass -- every
+// thread keeps an online (max, sum exp) and its own sorted top 9, then the
+// workgroup merges both in a fixed order.  EOT is -inf when state ?
+// state->step + 1 < min_tokens : suppress_fixed, and always when !eot_stop.
+// Larger lp first, equal lp: larger id first.  out_tok / out_lp: [rows][kp].
+// A non-finite raw logit sets *range_flag.  Needs V >= 16.
+hipError_t launch_beam_topk(const float* logits, int rows, int64_t ld, int V, int kp, int suppress_fixed, int min_tokens,
+                            int eot_stop, const DecodeState* state, int* out_tok, float* out_lp, int* range_flag,
+                            hipStream_t st);
+
+// Everything beam_select reads and writes, device pointers.  rows = n_clips *
+// K; row clip * K + j is beam j of its clip.
+struct BeamSelect {
+  const int* top_tok;   // [rows][K + 1]   beam_topk's pairs
+  const float* top_lp;  // [rows][K + 1]
+  float* S;             // [rows]          sums of the live beams, in place
+  int* next_tok;        // [rows]          the token each new beam feeds to the next step
+  int* parent;          // [rows]          the row each new beam continues
+  int* anc;             // [2][rows][ctx]  ancestor tables; the live one is ((step + 1) & 1)
+  int* fed;             // [ctx][rows]     fed[slot][row]: the token row fed at cache slot `slot`
+  float* fin_sum;       // [n_clips][C]    finished sequences: sum of log-probabilities,
+  int* fin_len;         // [n_clips][C]      tokens (EOT not counted),
+  int* fin_anc;         // [n_clips][C][ctx] and the ancestor row of every slot
+  int* fin_n;           // [n_clips]
+  int* complete;        // [n_clips]       sticky
+  int* ticket;          // [1]             arrival counter, zero between launches
+  DecodeState* state;   // advanced by the last workgroup to arrive
+};
+// One workgroup per clip: ranks the clip's K (K + 1) candidates (score =
+// S[j] + lp in f32; score descending, then source beam, then rank, both
+// ascending; -inf dropped), keeps the first K non-EOT ones as the next beams,
+// files the EOT ones met on the way (while the clip holds fewer than C and is
+// not complete), copies the ancestor rows into the other table and -- what
+// launch_bookkeep does for a greedy step -- advances position / kv_len / step.
+// state->n_done counts the complete clips.
+hipError_t launch_beam_select(const BeamSelect& a, int n_clips, int K, int C, int ctx, hipStream_t st);
+
+// The decode step's self-attention (Tq = 1) over a reindexed cache: key j <
+// kv_len of row r is read from cache row anc[r][j]; the row's new key / value
+// are appended at (r, kv_len) as launch_decoder_self_attention does.  anc:
+// [rows][ctx] int32; with state non-null the live table of a [2][rows][ctx]
+// pair is picked by (state->step + 1) & 1.  An identity table gives the bits of
+// launch_decoder_self_attention.
+hipError_t launch_decoder_self_attention_beam(const float* qkv, float* cache_k, float* cache_v, int rows, int H,
+                                              int ctx, const DecodeState* state, int kv_len_host, const int* anc,
+                                              _Float16* tiled, int ns, hipStream_t st, float* out32 = nullptr);
+
+}  // namespace wa

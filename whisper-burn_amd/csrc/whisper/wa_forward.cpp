@@ -71,9 +71,9 @@ bool lnfold_on(const wa_model* m, int Tq, const DecodeState* state, int64_t rows
 
 // A decode step of <= 32 clips picks its tokens inside the logits kernel
 // (wa::launch_logits_pick); prompts and larger groups keep the stored logits +
-// a separate pick.
-bool fused_pick(const DecGroup& g, int Tq, const DecodeState* state) {
-  return state != nullptr && Tq == 1 && g.nb <= 32;
+// a separate pick.  A beam call keeps the stored logits: its top-(K + 1) reads them.
+bool fused_pick(const DecGroup& g, const DecodeCall& call, int Tq, const DecodeState* state) {
+  return state != nullptr && Tq == 1 && g.nb <= 32 && call.beam_k == 0;
 }
 
 // The fused pick of group g in the call's mode: a scored call (call.score)
@@ -103,7 +103,7 @@ wq4_status decode_step(wa_model* m, DecGroup& g, const DecodeCall& call, hipStre
   WA_HIP(launch_bookkeep(g.next_tok, p.out_lp, g.tokens, call.score ? g.logprob : nullptr, g.ntok, g.done, g.nb,
                          kMaxTokens, call.eot_stop, g.state, call.ts ? g.ts_rules : nullptr, p.ts0, V, st));
   WA_TRY(decoder_forward(m, g, call, g.next_tok, 1, g.state, 0, 0, st));
-  if (fused_pick(g, 1, g.state)) return WQ4_OK;
+  if (fused_pick(g, call, 1, g.state)) return WQ4_OK;
   if (p.temp || p.rules) {  // the sampled (pick step + 1) or timestamp pick over the stored rows
     WA_HIP(launch_row_pick(g.logits, g.nb, V, V, 0, kMinTokens, g.state, p.rules, p.ts0, p.temp, p.seed, 0, g.next_tok,
                            g.next_lp, nullptr, m->range_flag, st));
@@ -427,8 +427,12 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
     DecLayer& L = m->dec[li];
     // self-attention
     WA_TRY(ln_gemm(L.qkv, L.qkv_b, L.qkv_wg, L.qkv_b2, L.ln1_w, L.ln1_b, g.qkvd, nullptr, 0u));
-    WA_HIP(launch_decoder_self_attention(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, Tq, H,
-                                         c.n_text_ctx, state, kv0, g.atd_dec, m->ns, st, a32, pad));
+    if (call.beam_k > 0 && state)  // a beam call's step: the caches through the rows' ancestor table
+      WA_HIP(launch_decoder_self_attention_beam(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, H,
+                                                c.n_text_ctx, state, kv0, m->bm.anc, g.atd_dec, m->ns, st, a32));
+    else
+      WA_HIP(launch_decoder_self_attention(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, Tq, H,
+                                           c.n_text_ctx, state, kv0, g.atd_dec, m->ns, st, a32, pad));
     WA_TRY(resid_gemm(L.out, L.out_b, g.atd_dec, a32, L.ln2_w));
     // cross-attention
     WA_TRY(ln_gemm(L.cq, L.cq_b, L.cq_wg, L.cq_b2, L.ln2_w, L.ln2_b, g.qd, nullptr, 0u));
@@ -455,7 +459,7 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
   }
   // final LN (decoder.rs:286 / 340) and tied-embedding logits of the last
   // position of every clip (decoder.rs:289-292, 342-343)
-  if (fused_pick(g, Tq, state)) {  // decode step: logits + the mode's pick in one kernel, into next_tok
+  if (fused_pick(g, call, Tq, state)) {  // decode step: logits + the mode's pick in one kernel, into next_tok
     // the final LN writes the pick's operand directly (A-tiled, the
     // embedding planes' precision)
     WA_WQ4(wq4_layernorm(g.xd, m->dln_w, m->dln_b, rows, D, m->prec, g.hid_t, nullptr, st));

@@ -18,6 +18,7 @@
 
 #include "../wq4_device.hpp"
 #include "../wq4_lnmath.hpp"
+#include "wa_beam.hpp"
 #include "wa_kernels.hpp"
 
 namespace wa {
@@ -884,6 +885,87 @@ hipError_t launch_decoder_self_attention(const float* qkv, float* cache_k, float
     if (Tq == 1) { WA_SELF(1, 1); } else { WA_SELF(1, 4); }
   }
 #undef WA_SELF
+  return hipGetLastError();
+}
+
+// The same step (Tq = 1) over a reindexed cache (beam search, wa_beam.hpp):
+// key j < kv_len of row b lives in cache row anc[b][j].  The row's table is
+// staged in LDS once, so a key's address waits on an LDS read, not on a
+// dependent global load.  Everything else -- the 4-wave key split, the 8-deep
+// scan, the merge, the epilogue -- is dec_self_attn_kernel<NS, 1>'s, so an
+// identity table gives its bits.  The caches never move: a row appends at its
+// own (b, kv_len), slots below kv_len are only read.
+template <int NS>
+__global__ __launch_bounds__(256) void dec_self_attn_beam_kernel(const float* __restrict__ qkv, float* __restrict__ ck,
+                                                                 float* __restrict__ cv, int H, int ctx,
+                                                                 const DecodeState* state, int kv_len_host,
+                                                                 const int* __restrict__ anc,
+                                                                 _Float16* __restrict__ tiled,
+                                                                 float* __restrict__ out32) {
+  __shared__ float wm[4][1], wl[4][1];
+  __shared__ float wo[4][1][64];
+  __shared__ int anc_s[kMaxCtx];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int head = blockIdx.x, b = blockIdx.y, rows = gridDim.y;
+  const int D = H * 64;
+  const int sub = lane & 15, grp = lane >> 4;
+  const int kv_len = state ? state->kv_len : kv_len_host;
+  // a pair of tables under a device state: beam_select writes the one the next step reads
+  const int* arow = anc + (state ? (size_t)((state->step + 1) & 1) * rows * ctx : 0) + (size_t)b * ctx;
+  for (int j = tid; j < kv_len; j += 256) anc_s[j] = max(0, min(arow[j], rows - 1));  // loads stay inside the caches
+  const size_t hb = ((size_t)b * H + head) * ctx * 64;
+  floatx4 qv[1];
+  const float* kb = ck + (size_t)head * ctx * 64 + sub * 4;
+  const float* vb = cv + (size_t)head * ctx * 64 + sub * 4;
+  const size_t row_stride = (size_t)H * ctx * 64;
+  const float* newb = qkv + (size_t)b * 3 * D + D + head * 64 + sub * 4;
+  if (tid < 16) {
+    const int s4 = tid * 4;
+    const float* src = qkv + (size_t)b * 3 * D + head * 64 + s4;
+    *reinterpret_cast<floatx4*>(ck + hb + (size_t)kv_len * 64 + s4) = *reinterpret_cast<const floatx4*>(src + D);
+    *reinterpret_cast<floatx4*>(cv + hb + (size_t)kv_len * 64 + s4) = *reinterpret_cast<const floatx4*>(src + 2 * D);
+  }
+  qv[0] = *reinterpret_cast<const floatx4*>(qkv + (size_t)b * 3 * D + head * 64 + sub * 4) * kEaQScale;
+  __syncthreads();  // the table is staged
+  const int nk = kv_len + 1;
+  const int per_wave = (nk + 3) / 4;
+  const int k0 = min(nk, wave * per_wave), k1 = min(nk, k0 + per_wave);
+  float m[1], l[1];
+  floatx4 o[1];
+  attn_scan<1, 8>(
+      qv, 1, k0, k1, grp,
+      [&](int j, const float*& kp, const float*& vp) {
+        if (j < kv_len) {
+          const size_t ofs = (size_t)anc_s[j] * row_stride + (size_t)j * 64;
+          kp = kb + ofs;
+          vp = vb + ofs;
+        } else {  // this step's own key: not yet visible through the cache
+          kp = newb;
+          vp = kp + D;
+        }
+      },
+      [&](int, int j) { return j <= kv_len; }, m, l, o);
+  float mn, ls, os;
+  attn_merge<1, 4>(1, wave, lane, m, l, o, wm, wl, wo, mn, ls, os);
+  if (wave < 1) {
+    const float val = os / ls;
+    const float v1 = __shfl_down(val, 1, 64), v2 = __shfl_down(val, 2, 64), v3 = __shfl_down(val, 3, 64);
+    if ((lane & 3) == 0) attn_store4<NS>(tiled, out32, D, b, head * 64 + lane, kbp_of(D), val, v1, v2, v3);
+  }
+}
+
+hipError_t launch_decoder_self_attention_beam(const float* qkv, float* cache_k, float* cache_v, int rows, int H,
+                                              int ctx, const DecodeState* state, int kv_len_host, const int* anc,
+                                              _Float16* tiled, int ns, hipStream_t st, float* out32) {
+  if (rows < 1 || H < 1 || ctx < 1 || ctx > kMaxCtx || !anc || (!state && (kv_len_host < 0 || kv_len_host >= ctx)))
+    return hipErrorInvalidValue;
+  const dim3 grid(H, rows), block(256);
+  if (ns == 2)
+    hipLaunchKernelGGL(dec_self_attn_beam_kernel<2>, grid, block, 0, st, qkv, cache_k, cache_v, H, ctx, state,
+                       kv_len_host, anc, tiled, out32);
+  else
+    hipLaunchKernelGGL(dec_self_attn_beam_kernel<1>, grid, block, 0, st, qkv, cache_k, cache_v, H, ctx, state,
+                       kv_len_host, anc, tiled, out32);
   return hipGetLastError();
 }
 

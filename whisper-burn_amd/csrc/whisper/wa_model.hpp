@@ -1,6 +1,6 @@
 // wa_model.hpp -- internal: the Whisper model runtime's state (struct
 // wa_model) and what its translation units (wa_weights, wa_forward,
-// wa_transcribe, wa_long, wa_prompt, wa_align, wa_api, wa_checks .cpp) need
+// wa_transcribe, wa_long, wa_prompt, wa_align, wa_beam, wa_api, wa_checks .cpp) need
 // from one another.
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -14,6 +14,7 @@
 #include "../../../include/whisper_amd.h"
 #include "../../../include/wq4.h"
 #include "wa_align.hpp"
+#include "wa_beam.hpp"
 #include "wa_gguf.hpp"
 #include "wa_kernels.hpp"
 #include "wa_pick.hpp"
@@ -186,6 +187,11 @@ struct DecGroup {
   };
   KeptGraph kept[kKeptGraphs];
   int kept_next = 0;  // the slot the next parked graph replaces once all are taken
+  // beam calls (wa_transcribe_beam): their step graph has a slot of its own,
+  // re-captured when what it bakes in changes (wa_beam.cpp, BeamKey); the
+  // graphs and keys above never see a beam call
+  hipGraphExec_t beam_graph = nullptr;
+  int beam_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
 };
 
 // One transcribe call's decode: built by its entry and passed down to every
@@ -223,6 +229,11 @@ struct DecodeCall {
   // model's alignment buffers (wa_model::Align; the group's F uploaded by the
   // entry) and stops there -- no logits, no scores
   bool align = false;
+  // beam calls (wa_transcribe_beam; 0 otherwise): beams per clip and finished
+  // sequences kept per clip.  The group's rows are clip * beam_k + beam; the
+  // steps read the self-attention caches through the ancestor table and keep
+  // the stored logits (no fused pick)
+  int beam_k = 0, beam_c = 0;
 
   DecodeCall() = default;
   DecodeCall(int lang, int max_tok, int eot, bool score_, bool ts_ = false, int max_initial = 50, bool sample_ = false)
@@ -378,6 +389,16 @@ struct wa_model {
     std::vector<std::pair<int, int>> pairs;
     float timings[4] = {0, 0, 0, 0};  // encoder, prefill with capture, DTW, total (ms) of the last wa_align
   } al;
+  // Beam search (wa_beam.cpp; allocated by the first wa_transcribe_beam,
+  // all or nothing): the pairs of beam_topk, the live sums, parents, the two
+  // ancestor tables, the fed tokens per cache slot and the finished lists
+  // (wa::BeamSelect), sized for bmax rows, kBeamMaxCand candidates, n_text_ctx.
+  struct Beam {
+    bool ok = false;
+    int *top_tok = nullptr, *parent = nullptr, *anc = nullptr, *fed = nullptr;
+    float *top_lp = nullptr, *S = nullptr, *fin_sum = nullptr;
+    int *fin_len = nullptr, *fin_anc = nullptr, *fin_n = nullptr, *complete = nullptr, *ticket = nullptr;
+  } bm;
   float timings[5] = {0, 0, 0, 0, 0};
   // every group's score / timestamp / sampling buffers are allocated
   // (prepare_call: by the first call in that mode, all or nothing)
@@ -412,6 +433,7 @@ struct wa_model {
     resolve_profile();
     for (auto& g : groups) {
       if (g.graph) (void)hipGraphExecDestroy(g.graph);
+      if (g.beam_graph) (void)hipGraphExecDestroy(g.beam_graph);
       for (auto& k : g.kept)
         if (k.exec) (void)hipGraphExecDestroy(k.exec);
       if (g.st) (void)hipStreamDestroy(g.st);
@@ -497,6 +519,8 @@ wq4_status transcribe_ladder(wa_model* m, const DecodeCall& call, const float* m
 // wa_transcribe's argument check (wa_prompt.cpp's entries share it)
 wq4_status check_args(const wa_model* m, bool ptrs_ok, int n_batches, int max_tokens, int n_clips,
                       const float* temps = nullptr, const int* rungs = nullptr);
+// one range tier up after a flagged run; WQ4_ERANGE at the last
+wq4_status raise_tier(wa_model* m);
 // a transcribe through the range tiers
 wq4_status transcribe_tiers(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,
                             int32_t* tokens_out, int32_t* n_tokens_out, void* stream, const wa_scores* scores);

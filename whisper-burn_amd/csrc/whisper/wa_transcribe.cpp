@@ -577,7 +577,7 @@ bool wa::bad_temperatures(const float* t, int n) {
 }
 
 // One range tier up after a flagged run (see transcribe_tiers); WQ4_ERANGE at the last.
-static wq4_status raise_tier(wa_model* m) {
+wq4_status wa::raise_tier(wa_model* m) {
   if (m->range_tier == 3)
     return fail(WQ4_ERANGE,
                 "activation overflow: an MFMA operand left the f16-pair range (|x| >= 4094 after every range tier: "

@@ -29,6 +29,20 @@ class Scores(ctypes.Structure):
                 ("lang_token", ctypes.POINTER(ctypes.c_int32)), ("lang_prob", ctypes.POINTER(ctypes.c_float))]
 
 
+class Beam(ctypes.Structure):
+    """struct wa_beam: beams per clip, finished sequences kept per clip, length penalty (NaN: none)."""
+
+    _fields_ = [("beam_size", ctypes.c_int), ("max_candidates", ctypes.c_int), ("length_penalty", ctypes.c_float)]
+
+
+class BeamResult(ctypes.Structure):
+    """struct wa_beam_result: host arrays, each nullable."""
+
+    _fields_ = [("cand_tokens", ctypes.POINTER(ctypes.c_int32)), ("cand_n_tokens", ctypes.POINTER(ctypes.c_int32)),
+                ("cand_sum_logprob", ctypes.POINTER(ctypes.c_float)), ("n_candidates", ctypes.POINTER(ctypes.c_int32)),
+                ("best", ctypes.POINTER(ctypes.c_int32))]
+
+
 class Segment(ctypes.Structure):
     """struct wa_segment: tokens [tok_begin, tok_end) from start_s to end_s."""
 
@@ -267,6 +281,16 @@ def lib() -> ctypes.CDLL:
         for n in ("wa_model_set_alignment_heads", "wa_align", "wa_last_align_timings", "wa_align_words",
                   "wa_alignment_heads_check", "wa_align_check",
                   "wa_align_matrix_check", "wa_dtw_check"):
+            getattr(L, n).restype = c_int
+        L.wa_transcribe_beam.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Beam), i32p, i32p, sp,
+                                         ctypes.POINTER(BeamResult), vp]
+        L.wa_beam_check.argtypes = [ctypes.POINTER(Beam), c_int, c_int]
+        L.wa_beam_rank.argtypes = [f32p, i32p, c_int, ctypes.c_float, i32p]
+        L.wa_beam_topk_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, i32p]
+        L.wa_beam_select_check.argtypes = [c_int] + [vp] * 13 + [c_int] * 4
+        L.wa_self_attention_beam_check.argtypes = [c_int, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
+        for n in ("wa_transcribe_beam", "wa_beam_check", "wa_beam_rank", "wa_beam_topk_check", "wa_beam_select_check",
+                  "wa_self_attention_beam_check"):
             getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
@@ -574,6 +598,75 @@ def self_attention_check(qkv, cache_k, cache_v, Tq: int, H: int, kv_len: int, pr
     check(lib().wa_self_attention_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, Tq, H,
                                         ctx, kv_len, precision, _ptr(out)))
     return out
+
+
+def self_attention_beam_check(qkv, cache_k, cache_v, anc, H: int, kv_len: int, precision: int = wq4.PREC_F16X2,
+                              f32_out: bool = False):
+    """The beam step's self-attention (wa_self_attention_beam_check): qkv cuda
+    f32 [R, 3*64H]; caches [R, H, ctx, 64] (updated in place: row r's new key /
+    value at (r, kv_len)); anc cuda int32 [R, ctx], key j < kv_len of row r is
+    read from cache row anc[r, j] -> [R, 64H].  anc None: the kernel of
+    self_attention_check itself; f32_out: the f32-row form of range tier 3."""
+    torch = _torch()
+    R, _, ctx, _ = cache_k.shape
+    if anc is not None:
+        assert anc.dtype == torch.int32 and anc.is_contiguous() and tuple(anc.shape) == (R, ctx)
+    out = torch.empty((R, 64 * H), device=qkv.device, dtype=torch.float32)
+    check(lib().wa_self_attention_beam_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v),
+                                             None if anc is None else _ptr(anc), R, H, ctx, kv_len, precision,
+                                             1 if f32_out else 0, _ptr(out)))
+    return out
+
+
+def beam_topk_check(logits, kp: int, step: int = -1, suppress_eot: bool = False, eot_stop: bool = True, tok=None,
+                    lp=None):
+    """The per-row log-softmax + top-kp kernel (wa_beam_topk_check): logits cuda
+    f32 [R, V] -> (tokens int32 [R, kp], log-probabilities f32 [R, kp], range
+    flag).  EOT is masked when not eot_stop, else suppress_eot (step < 0) or
+    step + 1 < 3 through a device state.  tok / lp: output tensors to write
+    into (flat, at least R * kp entries)."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    if tok is None:
+        tok = torch.empty((R, kp), device=logits.device, dtype=torch.int32)
+    if lp is None:
+        lp = torch.empty((R, kp), device=logits.device, dtype=torch.float32)
+    flag = ctypes.c_int32(0)
+    check(lib().wa_beam_topk_check(_dev(logits), _ptr(logits), R, V, kp, 1 if suppress_eot else 0, step,
+                                   1 if eot_stop else 0, _ptr(tok), _ptr(lp), ctypes.byref(flag)))
+    return tok, lp, int(flag.value)
+
+
+BEAM_SELECT_ARRAYS = ("top_tok", "top_lp", "S", "next_tok", "parent", "anc", "fed", "fin_sum", "fin_len", "fin_anc",
+                      "fin_n", "complete", "state")
+
+
+def beam_select_check(arrays: dict, n_clips: int, K: int, C: int, ctx: int) -> None:
+    """One merge step of the beam search in place on the caller's cuda tensors
+    (wa_beam_select_check; BEAM_SELECT_ARRAYS names them, shapes in
+    include/whisper_amd.h): consecutive calls are consecutive steps."""
+    t = [arrays[k] for k in BEAM_SELECT_ARRAYS]
+    assert all(x.is_cuda and x.is_contiguous() for x in t)
+    check(lib().wa_beam_select_check(_dev(t[0]), *[_ptr(x) for x in t], n_clips, K, C, ctx))
+
+
+def beam_check(beam_size: int, max_candidates: int, n_clips: int, max_batch: int, null: bool = False) -> int:
+    """wa_beam_check's status (0 = OK) for these arguments; null: a null wa_beam."""
+    b = Beam(int(beam_size), int(max_candidates), float("nan"))
+    return int(lib().wa_beam_check(None if null else ctypes.byref(b), n_clips, max_batch))
+
+
+def beam_rank(sum_logprob, n_tokens, length_penalty: Optional[float] = None) -> int:
+    """The rank of wa_transcribe_beam over one clip's candidates (wa_beam_rank)."""
+    s = np.ascontiguousarray(sum_logprob, np.float32)
+    n = np.ascontiguousarray(n_tokens, np.int32)
+    assert s.ndim == 1 and s.shape == n.shape
+    best = ctypes.c_int32(-1)
+    check(lib().wa_beam_rank(s.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                             n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(s.size),
+                             float("nan") if length_penalty is None else float(length_penalty), ctypes.byref(best)))
+    return int(best.value)
 
 
 def _prompt_arrays(prompts, n: Optional[int] = None, min_len: int = 1):
@@ -1032,6 +1125,42 @@ class WhisperModel:
                                   -1 if lang_token is None else int(lang_token), max_tokens, 1 if eot_stop else 0,
                                   toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), self._stream()))
         return [toks[b, : nt[b]].tolist() for b in range(B)]
+
+    def transcribe_beam(self, mel, beam_size: int = 5, patience: float = 1.0, length_penalty: Optional[float] = None,
+                        lang_token: Optional[int] = 50259, max_tokens: int = 224, eot_stop: bool = True,
+                        return_candidates: bool = False):
+        """Beam search (wa_transcribe_beam; OpenAI's beam_size / patience /
+        length_penalty): mel cuda f32 [B, n_mels, 3000] with B * beam_size <=
+        max_batch.  Returns the best candidate's token list per clip, or with
+        return_candidates a dict per clip: tokens, sum_logprob, best, candidates
+        (list order: dicts of tokens and sum_logprob), no_speech_prob,
+        lang_token, lang_prob."""
+        torch = _torch()
+        mel = mel.contiguous()
+        assert mel.dtype == torch.float32 and mel.is_cuda
+        B, K = mel.shape[0], int(beam_size)
+        C = int(round(K * patience))
+        toks = np.zeros((B, max_tokens), np.int32)
+        nt = np.zeros(B, np.int32)
+        ct = np.zeros((B, max(C, 1), max_tokens), np.int32)
+        cn, cs = np.zeros((B, max(C, 1)), np.int32), np.zeros((B, max(C, 1)), np.float32)
+        nc, best = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        ns, lpr, lt = np.zeros(B, np.float32), np.zeros(B, np.float32), np.zeros(B, np.int32)
+        i32p, f32p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+        sc = Scores(None, ns.ctypes.data_as(f32p), lt.ctypes.data_as(i32p), lpr.ctypes.data_as(f32p))
+        res = BeamResult(ct.ctypes.data_as(i32p), cn.ctypes.data_as(i32p), cs.ctypes.data_as(f32p),
+                         nc.ctypes.data_as(i32p), best.ctypes.data_as(i32p))
+        bm = Beam(K, C, float("nan") if length_penalty is None else float(length_penalty))
+        check(lib().wa_transcribe_beam(self._h, _ptr(mel), B, -1 if lang_token is None else int(lang_token),
+                                       max_tokens, 1 if eot_stop else 0, ctypes.byref(bm), toks.ctypes.data_as(i32p),
+                                       nt.ctypes.data_as(i32p), ctypes.byref(sc), ctypes.byref(res), self._stream()))
+        if not return_candidates:
+            return [toks[b, : nt[b]].tolist() for b in range(B)]
+        return [{"tokens": toks[b, : nt[b]].tolist(), "sum_logprob": float(cs[b, best[b]]), "best": int(best[b]),
+                 "candidates": [{"tokens": ct[b, i, : cn[b, i]].tolist(), "sum_logprob": float(cs[b, i])}
+                                for i in range(nc[b])],
+                 "no_speech_prob": float(ns[b]), "lang_token": int(lt[b]), "lang_prob": float(lpr[b])}
+                for b in range(B)]
 
     def transcribe_batches(self, mels, lang_token: Optional[int] = 50259, max_tokens: int = 224,
                            eot_stop: bool = True):
