@@ -12,6 +12,12 @@
 // run unchanged.  A step is decoder_forward (self-attention through the
 // ancestor table, stored logits), beam_topk and beam_select, captured once; the
 // host only polls the count of complete clips through the pinned ring.
+//
+// wa_transcribe_beam_ex adds the two modes of the greedy entries to it: under
+// the timestamp rules the rows' rule records (the group's, as in a greedy
+// timestamp decode) are read by the rules form of the top-k and follow the
+// reindexing in the merge; after caller prompts every row of a clip carries the
+// clip's prompt through the group's prefill and the steps run the pad forms.
 #include <cmath>
 
 #include "wa_model.hpp"
@@ -93,29 +99,44 @@ wq4_status ensure_beam(wa_model* m) {
   return WQ4_OK;
 }
 
-BeamSelect select_args(const wa_model* m, const DecGroup& g) {
+// (a timestamp call's rows keep their rule records where a greedy timestamp
+// decode keeps its clips': the group's, reset by prompt_group)
+BeamSelect select_args(const wa_model* m, const DecGroup& g, const DecodeCall& call) {
   const wa_model::Beam& b = m->bm;
-  return BeamSelect{b.top_tok, b.top_lp,  b.S,       g.next_tok, b.parent,   b.anc,    b.fed,
-                    b.fin_sum, b.fin_len, b.fin_anc, b.fin_n,    b.complete, b.ticket, g.state};
+  return BeamSelect{b.top_tok, b.top_lp,  b.S,       g.next_tok, b.parent,   b.anc,    b.fed,  b.fin_sum,
+                    b.fin_len, b.fin_anc, b.fin_n,   b.complete, b.ticket,   g.state,  call.ts ? g.ts_rules : nullptr};
+}
+
+// The top-(K + 1) of the group's stored logit rows and the per-clip merge, in
+// the call's mode: pick 0 (state null: EOT suppressed, whisper.rs:97-99) or a
+// step's (EOT by the state).
+wq4_status beam_pick(wa_model* m, DecGroup& g, const DecodeCall& call, const DecodeState* state, hipStream_t st) {
+  const int V = m->cfg.n_vocab, K = call.beam_k, ts0 = m->ts0();
+  if (call.ts)
+    WA_HIP(launch_beam_topk_rules(g.logits, g.nb, V, V, K + 1, state ? 0 : 1, state ? kMinTokens : 0, call.eot_stop,
+                                  state, g.ts_rules, ts0, m->bm.top_tok, m->bm.top_lp, nullptr, m->range_flag, st));
+  else
+    WA_HIP(launch_beam_topk(g.logits, g.nb, V, V, K + 1, state ? 0 : 1, state ? kMinTokens : 0, call.eot_stop, state,
+                            m->bm.top_tok, m->bm.top_lp, m->range_flag, st));
+  WA_HIP(launch_beam_select(select_args(m, g, call), g.nb / K, K, call.beam_c, m->cfg.n_text_ctx, st, ts0, V));
+  return WQ4_OK;
 }
 
 // One beam step on `st`: the decoder pass over the rows' last tokens, the
 // top-(K + 1) of every stored logit row, the per-clip merge (which advances
 // the state for the next step).
 wq4_status beam_step(wa_model* m, DecGroup& g, const DecodeCall& call, hipStream_t st) {
-  const int V = m->cfg.n_vocab, K = call.beam_k;
   WA_TRY(decoder_forward(m, g, call, g.next_tok, 1, g.state, 0, 0, st));
-  WA_HIP(launch_beam_topk(g.logits, g.nb, V, V, K + 1, 0, kMinTokens, call.eot_stop, g.state, m->bm.top_tok,
-                          m->bm.top_lp, m->range_flag, st));
-  WA_HIP(launch_beam_select(select_args(m, g), g.nb / K, K, call.beam_c, m->cfg.n_text_ctx, st));
-  return WQ4_OK;
+  return beam_pick(m, g, call, g.state, st);
 }
 
 // The beam step graph of group g: everything the capture bakes in is the key.
 wq4_status ensure_beam_graph(wa_model* m, DecGroup& g, const DecodeCall& call) {
-  const int key[8] = {call.beam_k,     call.beam_c,    g.nb,           call.eot_stop ? 1 : 0,
-                      m->range_tier,   m->group_kv(g) ? 1 : 0, g.xplan.splits, g.xres.q};
-  if (g.beam_graph && std::equal(key, key + 8, g.beam_key)) return WQ4_OK;
+  constexpr int kKey = sizeof(g.beam_key) / sizeof(g.beam_key[0]);
+  const int key[kKey] = {call.beam_k,   call.beam_c,            g.nb,           call.eot_stop ? 1 : 0,
+                         m->range_tier, m->group_kv(g) ? 1 : 0, g.xplan.splits, g.xres.q,
+                         call.ts ? 1 : 0, call.prompt ? 1 : 0};
+  if (g.beam_graph && std::equal(key, key + kKey, g.beam_key)) return WQ4_OK;
   if (g.beam_graph) {
     (void)hipGraphExecDestroy(g.beam_graph);
     g.beam_graph = nullptr;
@@ -130,7 +151,7 @@ wq4_status ensure_beam_graph(wa_model* m, DecGroup& g, const DecodeCall& call) {
   ce = hipGraphInstantiate(&g.beam_graph, gr, nullptr, nullptr, 0);
   (void)hipGraphDestroy(gr);
   if (ce != hipSuccess) return fail(WQ4_EHIP, std::string("graph instantiate: ") + hipGetErrorString(ce));
-  std::copy(key, key + 8, g.beam_key);
+  std::copy(key, key + kKey, g.beam_key);
   return WQ4_OK;
 }
 
@@ -195,9 +216,7 @@ wq4_status beam_once(wa_model* m, const DecodeCall& call, const float* mel_dev, 
   WA_HIP(hipMemsetAsync(bm.complete, 0, (size_t)n_clips * 4, gs));
   WA_HIP(hipMemsetAsync(bm.ticket, 0, sizeof(int), gs));
   // pick 0: EOT suppressed (whisper.rs:97-99), then the first merge
-  WA_HIP(launch_beam_topk(g.logits, rows, c.n_vocab, c.n_vocab, K + 1, 1, 0, call.eot_stop, nullptr, bm.top_tok,
-                          bm.top_lp, m->range_flag, gs));
-  WA_HIP(launch_beam_select(select_args(m, g), n_clips, K, C, ctx, gs));
+  WA_TRY(beam_pick(m, g, call, nullptr, gs));
   WA_HIP(hipEventRecord(e_prompt, gs));
   WA_TRY(ensure_beam_graph(m, g, call));
 
@@ -313,12 +332,40 @@ wq4_status wa_beam_rank(const float* sum_logprob, const int32_t* n_tokens, int n
 wq4_status wa_transcribe_beam(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                               int eot_stop, const wa_beam* beam, int32_t* tokens_out, int32_t* n_tokens_out,
                               const wa_scores* scores, wa_beam_result* result, void* stream) {
+  return wa_transcribe_beam_ex(m, mel_dev, n_clips, lang_token, max_tokens, eot_stop, beam, nullptr, tokens_out,
+                               n_tokens_out, scores, result, stream);
+}
+
+wq4_status wa_transcribe_beam_ex(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
+                                 int eot_stop, const wa_beam* beam, const wa_beam_options* options,
+                                 int32_t* tokens_out, int32_t* n_tokens_out, const wa_scores* scores,
+                                 wa_beam_result* result, void* stream) {
   WA_TRY(check_args(m, mel_dev && tokens_out && n_tokens_out && beam, 1, max_tokens, n_clips));
   WA_TRY(check_beam(beam, n_clips, m->bmax));
-  DecodeCall call(lang_token, max_tokens, eot_stop, scores != nullptr);
+  const wa_prompt* prompt = options ? options->prompt : nullptr;
+  if (prompt) WA_TRY(check_prompt(m, prompt, n_clips, max_tokens));
+  const bool ts = options && options->timestamps != 0;
+  // (a timestamp call is a scored one, like every pick under the rules)
+  DecodeCall call(prompt ? -1 : lang_token, max_tokens, eot_stop, scores != nullptr, ts,
+                  ts ? options->max_initial : 50);
   call.beam_k = beam->beam_size;
   call.beam_c = beam->max_candidates;
+  // clip c's prompt on each of its K rows: the prefill is the group's, over the rows
+  const int K = call.beam_k;
+  std::vector<int32_t> row_tok, row_n;
+  wa_prompt row_prompt{};
+  if (prompt) {
+    row_tok.resize((size_t)n_clips * K * prompt->ld);
+    row_n.resize((size_t)n_clips * K);
+    for (int r = 0; r < n_clips * K; ++r) {
+      row_n[r] = prompt->n_tokens[r / K];
+      std::copy_n(prompt->tokens + (size_t)(r / K) * prompt->ld, prompt->ld, row_tok.begin() + (size_t)r * prompt->ld);
+    }
+    row_prompt = wa_prompt{row_tok.data(), row_n.data(), prompt->ld};
+    call.prompt = &row_prompt;
+  }
   WA_TRY(prepare_call(m, call));
+  if (prompt) WA_TRY(ensure_prefill(m));
   WA_TRY(ensure_beam(m));
   const int C = call.beam_c;
   std::vector<Candidates> cands;

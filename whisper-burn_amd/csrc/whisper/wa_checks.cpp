@@ -224,6 +224,95 @@ wq4_status wa_beam_select_check(int device, const int32_t* top_tok_dev, const fl
   return WQ4_OK;
 }
 
+wq4_status wa_beam_topk_rules_check(int device, const float* logits_dev, int n_rows, int V, int kp, int suppress_eot,
+                                    int step, int eot_stop, int ts0, const int32_t* records, int32_t* tok_dev,
+                                    float* lp_dev, int32_t* mass_dev, int32_t* flag_out) {
+  if (!logits_dev || !tok_dev || !lp_dev || !records) return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || V < 16 || kp < 2 || kp > kBeamMaxTop || ts0 <= 50257 || ts0 > V)
+    return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  auto* flag = d.alloc<int>(1);
+  auto* rules = d.alloc<TsRule>(n_rows);
+  DecodeState* st = step >= 0 ? d.alloc<DecodeState>(1) : nullptr;
+  if (!flag || !rules || (step >= 0 && !st)) return fail(WQ4_ENOMEM, "allocation failed");
+  if (st) {
+    const DecodeState s0{0, 0, step, 0};
+    WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  }
+  WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
+  WA_HIP(hipMemset(flag, 0, sizeof(int)));
+  WA_HIP(launch_beam_topk_rules(logits_dev, n_rows, V, V, kp, suppress_eot, kMinTokens, eot_stop, st, rules, ts0,
+                                tok_dev, lp_dev, mass_dev, flag, nullptr));
+  int f = 0;
+  WA_HIP(hipMemcpy(&f, flag, sizeof(int), hipMemcpyDeviceToHost));
+  if (flag_out) *flag_out = f;
+  return WQ4_OK;
+}
+
+wq4_status wa_beam_select_rules_check(int device, const int32_t* top_tok_dev, const float* top_lp_dev, float* S_dev,
+                                      int32_t* next_tok_dev, int32_t* parent_dev, int32_t* anc_dev, int32_t* fed_dev,
+                                      float* fin_sum_dev, int32_t* fin_len_dev, int32_t* fin_anc_dev,
+                                      int32_t* fin_n_dev, int32_t* complete_dev, int32_t* state_dev,
+                                      int32_t* records_dev, int ts0, int V, int n_clips, int K, int C, int ctx) {
+  if (!top_tok_dev || !top_lp_dev || !S_dev || !next_tok_dev || !parent_dev || !anc_dev || !fed_dev || !fin_sum_dev ||
+      !fin_len_dev || !fin_anc_dev || !fin_n_dev || !complete_dev || !state_dev)
+    return fail(WQ4_EINVAL, "null argument");
+  if (n_clips < 1 || n_clips > 512 || K < 1 || K > kBeamMaxK || C < K || C > kBeamMaxCand || ctx < 2 || ctx > 448 ||
+      (records_dev && (ts0 < 1 || V < ts0)))
+    return fail(WQ4_EINVAL, "bad sizes");
+  WA_HIP(hipSetDevice(device));
+  DecodeState s0;
+  WA_HIP(hipMemcpy(&s0, state_dev, sizeof(s0), hipMemcpyDeviceToHost));
+  if (s0.kv_len < 0 || s0.kv_len >= ctx) return fail(WQ4_EINVAL, "need 0 <= kv_len < ctx");
+  std::vector<int32_t> fin_n(n_clips);
+  WA_HIP(hipMemcpy(fin_n.data(), fin_n_dev, (size_t)n_clips * 4, hipMemcpyDeviceToHost));
+  for (int n : fin_n)
+    if (n < 0 || n > C) return fail(WQ4_EINVAL, "fin_n outside [0, C]");
+  Dev d;
+  auto* ticket = d.alloc<int>(1);
+  if (!ticket) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemset(ticket, 0, sizeof(int)));
+  const BeamSelect a{top_tok_dev, top_lp_dev,  S_dev,       next_tok_dev, parent_dev,   anc_dev, fed_dev,
+                     fin_sum_dev, fin_len_dev, fin_anc_dev, fin_n_dev,    complete_dev, ticket,
+                     reinterpret_cast<DecodeState*>(state_dev), reinterpret_cast<TsRule*>(records_dev)};
+  WA_HIP(launch_beam_select(a, n_clips, K, C, ctx, nullptr, ts0, V));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+wq4_status wa_self_attention_beam_pad_check(int device, const float* qkv_dev, float* cache_k_dev, float* cache_v_dev,
+                                            const int32_t* anc_dev, const int32_t* pad, int n_rows, int H, int ctx,
+                                            int kv_len, wq4_precision prec, int f32_out, float* out_dev) {
+  if (!qkv_dev || !cache_k_dev || !cache_v_dev || !anc_dev || !pad || !out_dev)
+    return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || H < 1 || ctx < 1 || ctx > 448 || kv_len < 0 || kv_len + 1 > ctx)
+    return fail(WQ4_EINVAL, "bad sizes");
+  for (int r = 0; r < n_rows; ++r)
+    if (pad[r] < 0 || pad[r] > kv_len) return fail(WQ4_EINVAL, "pad outside [0, kv_len]");
+  WA_HIP(hipSetDevice(device));
+  std::vector<int32_t> anc((size_t)n_rows * ctx);  // every entry read names a cache row
+  WA_HIP(hipMemcpy(anc.data(), anc_dev, anc.size() * 4, hipMemcpyDeviceToHost));
+  for (int r = 0; r < n_rows; ++r)
+    for (int j = pad[r]; j < kv_len; ++j)
+      if (anc[(size_t)r * ctx + j] < 0 || anc[(size_t)r * ctx + j] >= n_rows)
+        return fail(WQ4_EINVAL, "ancestor row outside [0, n_rows)");
+  Dev d;
+  auto* pad_dev = d.alloc<int>(n_rows);
+  if (!pad_dev) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemcpy(pad_dev, pad, (size_t)n_rows * 4, hipMemcpyHostToDevice));
+  auto launch = [&](_Float16* tiled, float* out32) {
+    return launch_decoder_self_attention_beam(qkv_dev, cache_k_dev, cache_v_dev, n_rows, H, ctx, nullptr, kv_len,
+                                              anc_dev, tiled, planes(prec), nullptr, out32, pad_dev);
+  };
+  if (f32_out) {
+    WA_HIP(launch(nullptr, out_dev));
+    WA_HIP(hipDeviceSynchronize());
+    return WQ4_OK;
+  }
+  return tiled_check(d, n_rows, 64 * H, prec, out_dev, [&](_Float16* tiled) { return launch(tiled, nullptr); });
+}
+
 wq4_status wa_conv_gelu_check(int device, const float* in_dev, int64_t in_bs, int64_t in_cs, int64_t in_ts, int B,
                               int C, int T_in, int stride, const float* w_dev, const float* bias_dev,
                               const float* pos_dev, int N, float* out_dev) {

@@ -429,7 +429,7 @@ wq4_status decoder_forward(wa_model* m, DecGroup& g, const DecodeCall& call, con
     WA_TRY(ln_gemm(L.qkv, L.qkv_b, L.qkv_wg, L.qkv_b2, L.ln1_w, L.ln1_b, g.qkvd, nullptr, 0u));
     if (call.beam_k > 0 && state)  // a beam call's step: the caches through the rows' ancestor table
       WA_HIP(launch_decoder_self_attention_beam(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, H,
-                                                c.n_text_ctx, state, kv0, m->bm.anc, g.atd_dec, m->ns, st, a32));
+                                                c.n_text_ctx, state, kv0, m->bm.anc, g.atd_dec, m->ns, st, a32, pad));
     else
       WA_HIP(launch_decoder_self_attention(g.qkvd, lane.cache_k[li] + self_ofs, lane.cache_v[li] + self_ofs, B, Tq, H,
                                            c.n_text_ctx, state, kv0, g.atd_dec, m->ns, st, a32, pad));

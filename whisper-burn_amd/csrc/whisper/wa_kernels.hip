@@ -900,6 +900,7 @@ __global__ __launch_bounds__(256) void dec_self_attn_beam_kernel(const float* __
                                                                  float* __restrict__ cv, int H, int ctx,
                                                                  const DecodeState* state, int kv_len_host,
                                                                  const int* __restrict__ anc,
+                                                                 const int* __restrict__ pad,
                                                                  _Float16* __restrict__ tiled,
                                                                  float* __restrict__ out32) {
   __shared__ float wm[4][1], wl[4][1];
@@ -927,9 +928,12 @@ __global__ __launch_bounds__(256) void dec_self_attn_beam_kernel(const float* __
   }
   qv[0] = *reinterpret_cast<const floatx4*>(qkv + (size_t)b * 3 * D + head * 64 + sub * 4) * kEaQScale;
   __syncthreads();  // the table is staged
-  const int nk = kv_len + 1;
+  // a right-aligned prompt: as dec_self_attn_kernel, the row's entries start at
+  // slot pad_b and the waves split the keys counted from there
+  const int pad_b = pad ? pad[b] : 0;
+  const int nk = kv_len + 1 - pad_b;
   const int per_wave = (nk + 3) / 4;
-  const int k0 = min(nk, wave * per_wave), k1 = min(nk, k0 + per_wave);
+  const int k0 = pad_b + min(nk, wave * per_wave), k1 = min(pad_b + nk, k0 + per_wave);
   float m[1], l[1];
   floatx4 o[1];
   attn_scan<1, 8>(
@@ -956,16 +960,16 @@ __global__ __launch_bounds__(256) void dec_self_attn_beam_kernel(const float* __
 
 hipError_t launch_decoder_self_attention_beam(const float* qkv, float* cache_k, float* cache_v, int rows, int H,
                                               int ctx, const DecodeState* state, int kv_len_host, const int* anc,
-                                              _Float16* tiled, int ns, hipStream_t st, float* out32) {
+                                              _Float16* tiled, int ns, hipStream_t st, float* out32, const int* pad) {
   if (rows < 1 || H < 1 || ctx < 1 || ctx > kMaxCtx || !anc || (!state && (kv_len_host < 0 || kv_len_host >= ctx)))
     return hipErrorInvalidValue;
   const dim3 grid(H, rows), block(256);
   if (ns == 2)
     hipLaunchKernelGGL(dec_self_attn_beam_kernel<2>, grid, block, 0, st, qkv, cache_k, cache_v, H, ctx, state,
-                       kv_len_host, anc, tiled, out32);
+                       kv_len_host, anc, pad, tiled, out32);
   else
     hipLaunchKernelGGL(dec_self_attn_beam_kernel<1>, grid, block, 0, st, qkv, cache_k, cache_v, H, ctx, state,
-                       kv_len_host, anc, tiled, out32);
+                       kv_len_host, anc, pad, tiled, out32);
   return hipGetLastError();
 }
 

@@ -191,7 +191,7 @@ struct DecGroup {
   // re-captured when what it bakes in changes (wa_beam.cpp, BeamKey); the
   // graphs and keys above never see a beam call
   hipGraphExec_t beam_graph = nullptr;
-  int beam_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  int beam_key[10] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 };
 
 // One transcribe call's decode: built by its entry and passed down to every

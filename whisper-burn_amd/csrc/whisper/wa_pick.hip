@@ -11,6 +11,7 @@
 
 #include "../wq4_device.hpp"
 #include "wa_pick.hpp"
+#include "wa_tsrule.hpp"
 
 // WA_LOGITS_NT (default on): the decode step's 266-MB embedding-table stream
 // (logits_argmax_f16_k32_kernel) with the nontemporal policy, so it does not
@@ -145,29 +146,8 @@ hipError_t launch_argmax_step(const float* logits, int B, int V, int min_tokens,
 }
 
 // ------------------------------------------------- timestamp rules --
-// The rule record's history update (TsRule, wa_pick.hpp): the one
-// statement of rules c and d, shared by the bookkeeping kernel and the host.
-__host__ __device__ inline TsRule ts_rule_step(const TsRule& r, int tok, int ts0, int V) {
-  TsRule n;
-  n.first = 0;
-  n.penult = (r.first || r.last) ? 1 : 0;
-  n.last = tok >= ts0 ? 1 : 0;
-  n.t_last = n.last ? tok : r.t_last;
-  n.ts_hi = V - 1;
-  if (n.last && n.penult) {  // a closed pair (or a lone first timestamp): text next, no timestamp
-    n.text_ok = 1;
-    n.ts_lo = V;
-  } else if (n.last) {  // text then a timestamp: its partner (>= it) or EOT
-    n.text_ok = 0;
-    n.ts_lo = n.t_last;
-  } else {  // text: more text, or a timestamp past the last one
-    n.text_ok = 1;
-    n.ts_lo = n.t_last >= 0 ? n.t_last + 1 : ts0;
-  }
-  n.pad = 0;
-  return n;
-}
-
+// The rule record's history update (ts_rule_step) and the masks a-e read from
+// a record (ts_masked): wa_tsrule.hpp, shared with the beam search's kernels.
 TsRule ts_rule_first(int ts0, int V, int max_initial) {
   TsRule r{};
   r.text_ok = 0;
@@ -181,16 +161,6 @@ TsRule ts_rule_first(int ts0, int V, int max_initial) {
 }
 
 TsRule ts_rule_next(const TsRule& r, int tok, int ts0, int V) { return ts_rule_step(r, tok, ts0, V); }
-
-// Masks a-e for one id of a row: r = the record's (text_ok, ts_lo, ts_hi,
-// first).  The one statement of the masks, shared by the fused and the
-// stored-logits pick.
-__device__ __forceinline__ bool ts_masked(int id, int ts0, const int4& r, bool suppress_eot) {
-  if (id >= ts0) return id < r.y || id > r.z;        // timestamps: the allowed range only (c, d, e)
-  if (id > kEOT) return true;                         // the specials (b)
-  if (id == kEOT) return suppress_eot || r.w != 0;    // a, and the first pick (e)
-  return r.x == 0;                                    // text (c, e)
-}
 
 // The mass rule and the pick from a row's two sides: (mt, it) the best text
 // candidate with st = sum exp(z - mt) over the text side, (mx, ix, sx) the

@@ -35,6 +35,12 @@ class Beam(ctypes.Structure):
     _fields_ = [("beam_size", ctypes.c_int), ("max_candidates", ctypes.c_int), ("length_penalty", ctypes.c_float)]
 
 
+class BeamOptions(ctypes.Structure):
+    """struct wa_beam_options: timestamp rules, their max_initial, one caller prompt per clip (nullable)."""
+
+    _fields_ = [("timestamps", ctypes.c_int), ("max_initial", ctypes.c_int), ("prompt", ctypes.c_void_p)]
+
+
 class BeamResult(ctypes.Structure):
     """struct wa_beam_result: host arrays, each nullable."""
 
@@ -289,8 +295,16 @@ def lib() -> ctypes.CDLL:
         L.wa_beam_topk_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, i32p]
         L.wa_beam_select_check.argtypes = [c_int] + [vp] * 13 + [c_int] * 4
         L.wa_self_attention_beam_check.argtypes = [c_int, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
+        L.wa_transcribe_beam_ex.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Beam),
+                                            ctypes.POINTER(BeamOptions), i32p, i32p, sp, ctypes.POINTER(BeamResult), vp]
+        L.wa_beam_topk_rules_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, i32p, vp, vp,
+                                               vp, i32p]
+        L.wa_beam_select_rules_check.argtypes = [c_int] + [vp] * 14 + [c_int] * 6
+        L.wa_self_attention_beam_pad_check.argtypes = [c_int, vp, vp, vp, vp, i32p, c_int, c_int, c_int, c_int, c_int,
+                                                       c_int, vp]
         for n in ("wa_transcribe_beam", "wa_beam_check", "wa_beam_rank", "wa_beam_topk_check", "wa_beam_select_check",
-                  "wa_self_attention_beam_check"):
+                  "wa_self_attention_beam_check", "wa_transcribe_beam_ex", "wa_beam_topk_rules_check",
+                  "wa_beam_select_rules_check", "wa_self_attention_beam_pad_check"):
             getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
@@ -649,6 +663,60 @@ def beam_select_check(arrays: dict, n_clips: int, K: int, C: int, ctx: int) -> N
     t = [arrays[k] for k in BEAM_SELECT_ARRAYS]
     assert all(x.is_cuda and x.is_contiguous() for x in t)
     check(lib().wa_beam_select_check(_dev(t[0]), *[_ptr(x) for x in t], n_clips, K, C, ctx))
+
+
+def beam_topk_rules_check(logits, kp: int, records, ts0: int, step: int = -1, suppress_eot: bool = False,
+                          eot_stop: bool = True, tok=None, lp=None, mass=None):
+    """beam_topk_check under the timestamp rules (wa_beam_topk_rules_check):
+    records int32 [R, 8], one rule record per row (timestamp_rule) -> (tokens
+    int32 [R, kp], log-probabilities f32 [R, kp], mass int32 [R]: 1 where rule f
+    fired, range flag).  A row with fewer than kp allowed ids ends in (0, -inf)
+    entries.  tok / lp / mass: output tensors to write into (flat)."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    rec = np.ascontiguousarray(records, np.int32)
+    assert rec.shape == (R, 8)
+    if tok is None:
+        tok = torch.empty((R, kp), device=logits.device, dtype=torch.int32)
+    if lp is None:
+        lp = torch.empty((R, kp), device=logits.device, dtype=torch.float32)
+    if mass is None:
+        mass = torch.empty(R, device=logits.device, dtype=torch.int32)
+    flag = ctypes.c_int32(0)
+    check(lib().wa_beam_topk_rules_check(_dev(logits), _ptr(logits), R, V, kp, 1 if suppress_eot else 0, step,
+                                         1 if eot_stop else 0, int(ts0),
+                                         rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(tok), _ptr(lp),
+                                         _ptr(mass), ctypes.byref(flag)))
+    return tok, lp, mass, int(flag.value)
+
+
+def beam_select_rules_check(arrays: dict, n_clips: int, K: int, C: int, ctx: int, ts0: int, V: int) -> None:
+    """beam_select_check with the rows' rule records, arrays["records"] cuda int32
+    [rows, 8] (None: the plain launch), advanced in place
+    (wa_beam_select_rules_check)."""
+    t = [arrays[k] for k in BEAM_SELECT_ARRAYS]
+    rec = arrays.get("records")
+    assert all(x.is_cuda and x.is_contiguous() for x in t) and (rec is None or (rec.is_cuda and rec.is_contiguous()))
+    check(lib().wa_beam_select_rules_check(_dev(t[0]), *[_ptr(x) for x in t], None if rec is None else _ptr(rec),
+                                           int(ts0), int(V), n_clips, K, C, ctx))
+
+
+def self_attention_beam_pad_check(qkv, cache_k, cache_v, anc, pad, H: int, kv_len: int,
+                                  precision: int = wq4.PREC_F16X2, f32_out: bool = False):
+    """self_attention_beam_check in the pad form of a prompted beam step
+    (wa_self_attention_beam_pad_check): pad host int32 [R], row r attends slots
+    [pad[r], kv_len] through anc."""
+    torch = _torch()
+    R, _, ctx, _ = cache_k.shape
+    assert anc.dtype == torch.int32 and anc.is_contiguous() and tuple(anc.shape) == (R, ctx)
+    pad = _i32(pad)
+    assert pad.size == R
+    out = torch.empty((R, 64 * H), device=qkv.device, dtype=torch.float32)
+    check(lib().wa_self_attention_beam_pad_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v),
+                                                 _ptr(anc), _as(pad, ctypes.c_int32), R, H, ctx, kv_len, precision,
+                                                 1 if f32_out else 0, _ptr(out)))
+    return out
 
 
 def beam_check(beam_size: int, max_candidates: int, n_clips: int, max_batch: int, null: bool = False) -> int:
@@ -1128,13 +1196,20 @@ class WhisperModel:
 
     def transcribe_beam(self, mel, beam_size: int = 5, patience: float = 1.0, length_penalty: Optional[float] = None,
                         lang_token: Optional[int] = 50259, max_tokens: int = 224, eot_stop: bool = True,
-                        return_candidates: bool = False):
+                        return_candidates: bool = False, timestamps: bool = False, max_initial: int = 50,
+                        prompts=None):
         """Beam search (wa_transcribe_beam; OpenAI's beam_size / patience /
         length_penalty): mel cuda f32 [B, n_mels, 3000] with B * beam_size <=
         max_batch.  Returns the best candidate's token list per clip, or with
         return_candidates a dict per clip: tokens, sum_logprob, best, candidates
         (list order: dicts of tokens and sum_logprob), no_speech_prob,
-        lang_token, lang_prob."""
+        lang_token, lang_prob.
+        timestamps / max_initial: the prompt and rules of transcribe_timestamps
+        (wa_transcribe_beam_ex); every returned clip and candidate then also
+        carries segments and seek_frames (segments_from_tokens), so a dict per
+        clip is returned in any case.  prompts: one id sequence per clip, as
+        transcribe_prompted (lang_token is ignored; with timestamps the prompt
+        leaves NO_TIMESTAMPS out)."""
         torch = _torch()
         mel = mel.contiguous()
         assert mel.dtype == torch.float32 and mel.is_cuda
@@ -1151,16 +1226,33 @@ class WhisperModel:
         res = BeamResult(ct.ctypes.data_as(i32p), cn.ctypes.data_as(i32p), cs.ctypes.data_as(f32p),
                          nc.ctypes.data_as(i32p), best.ctypes.data_as(i32p))
         bm = Beam(K, C, float("nan") if length_penalty is None else float(length_penalty))
-        check(lib().wa_transcribe_beam(self._h, _ptr(mel), B, -1 if lang_token is None else int(lang_token),
-                                       max_tokens, 1 if eot_stop else 0, ctypes.byref(bm), toks.ctypes.data_as(i32p),
-                                       nt.ctypes.data_as(i32p), ctypes.byref(sc), ctypes.byref(res), self._stream()))
-        if not return_candidates:
+        if timestamps or prompts is not None:
+            pr = None
+            if prompts is not None:
+                ptok, pn, pld = _prompt_arrays(prompts, B)
+                pr = Prompt(ptok.ctypes.data_as(i32p), pn.ctypes.data_as(i32p), pld)
+            opt = BeamOptions(1 if timestamps else 0, int(max_initial),
+                              None if pr is None else ctypes.cast(ctypes.pointer(pr), ctypes.c_void_p))
+            check(lib().wa_transcribe_beam_ex(self._h, _ptr(mel), B, -1 if lang_token is None else int(lang_token),
+                                              max_tokens, 1 if eot_stop else 0, ctypes.byref(bm), ctypes.byref(opt),
+                                              toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), ctypes.byref(sc),
+                                              ctypes.byref(res), self._stream()))
+        else:
+            check(lib().wa_transcribe_beam(self._h, _ptr(mel), B, -1 if lang_token is None else int(lang_token),
+                                           max_tokens, 1 if eot_stop else 0, ctypes.byref(bm),
+                                           toks.ctypes.data_as(i32p), nt.ctypes.data_as(i32p), ctypes.byref(sc),
+                                           ctypes.byref(res), self._stream()))
+        if not return_candidates and not timestamps:
             return [toks[b, : nt[b]].tolist() for b in range(B)]
-        return [{"tokens": toks[b, : nt[b]].tolist(), "sum_logprob": float(cs[b, best[b]]), "best": int(best[b]),
-                 "candidates": [{"tokens": ct[b, i, : cn[b, i]].tolist(), "sum_logprob": float(cs[b, i])}
-                                for i in range(nc[b])],
-                 "no_speech_prob": float(ns[b]), "lang_token": int(lt[b]), "lang_prob": float(lpr[b])}
-                for b in range(B)]
+        out = [{"tokens": toks[b, : nt[b]].tolist(), "sum_logprob": float(cs[b, best[b]]), "best": int(best[b]),
+                "candidates": [{"tokens": ct[b, i, : cn[b, i]].tolist(), "sum_logprob": float(cs[b, i])}
+                               for i in range(nc[b])],
+                "no_speech_prob": float(ns[b]), "lang_token": int(lt[b]), "lang_prob": float(lpr[b])}
+               for b in range(B)]
+        if timestamps:
+            for c in out:
+                self._timestamped([c] + c["candidates"])
+        return out
 
     def transcribe_batches(self, mels, lang_token: Optional[int] = 50259, max_tokens: int = 224,
                            eot_stop: bool = True):
