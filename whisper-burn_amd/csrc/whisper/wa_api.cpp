@@ -144,6 +144,46 @@ wq4_status wa_model_config(const wa_model* m, int32_t* cfg) {
 
 size_t wa_model_device_bytes(const wa_model* m) { return m ? m->bytes : 0; }
 
+wq4_status wa_model_set_suppress(wa_model* m, const int32_t* always, int n_always, const int32_t* first, int n_first) {
+  if (!m) return fail(WQ4_EINVAL, "null model");
+  WA_TRY(wa_suppress_check(always, n_always, first, n_first, m->ts0()));  // host only: nothing is set on failure
+  WA_HIP(hipSetDevice(m->device));
+  const int V = m->cfg.n_vocab;
+  const size_t W = (size_t)sup_mask_words(V);
+  if (n_always + n_first > 0) {
+    if (!m->sup_buf) {
+      m->sup_buf = m->dev.alloc<uint32_t>(2 * W);
+      if (!m->sup_buf) return fail(WQ4_ENOMEM, "suppress mask allocation failed");
+      m->bytes += 2 * W * sizeof(uint32_t);
+    }
+    // [0, W): always; [W, 2 W): always | first
+    std::vector<int32_t> both(always, always + n_always);
+    both.insert(both.end(), first, first + n_first);
+    std::vector<uint32_t> words(2 * W);
+    sup_mask_build(always, n_always, V, words.data());
+    sup_mask_build(both.data(), (int)both.size(), V, words.data() + W);
+    WA_HIP(hipDeviceSynchronize());  // no earlier call still reads the masks
+    WA_HIP(hipMemcpy(m->sup_buf, words.data(), 2 * W * sizeof(uint32_t), hipMemcpyHostToDevice));
+    m->sup_mask = m->sup_buf;
+    m->sup_mask0 = m->sup_buf + W;
+  } else {
+    m->sup_mask = m->sup_mask0 = nullptr;
+  }
+  m->sup_always.assign(always, always + n_always);
+  m->sup_first.assign(first, first + n_first);
+  m->drop_graphs();
+  return WQ4_OK;
+}
+
+wq4_status wa_model_suppress_ids(const wa_model* m, int which, int32_t* out, int cap, int* n) {
+  if (!m || !n || (which != 0 && which != 1)) return fail(WQ4_EINVAL, "bad arguments");
+  const std::vector<int32_t>& ids = which ? m->sup_first : m->sup_always;
+  *n = (int)ids.size();
+  if (cap < *n || (*n > 0 && !out)) return fail(WQ4_EINVAL, "out holds fewer ids than the list");
+  std::copy(ids.begin(), ids.end(), out);
+  return WQ4_OK;
+}
+
 wq4_status wa_last_timings(const wa_model* m, float* out) {
   if (!m || !out) return fail(WQ4_EINVAL, "null argument");
   std::memcpy(out, m->timings, sizeof(m->timings));

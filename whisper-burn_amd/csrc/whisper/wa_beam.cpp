@@ -109,15 +109,18 @@ BeamSelect select_args(const wa_model* m, const DecGroup& g, const DecodeCall& c
 
 // The top-(K + 1) of the group's stored logit rows and the per-clip merge, in
 // the call's mode: pick 0 (state null: EOT suppressed, whisper.rs:97-99) or a
-// step's (EOT by the state).
+// step's (EOT by the state); under the suppress mask of that pick (pick 0: the
+// union), if the model has lists.
 wq4_status beam_pick(wa_model* m, DecGroup& g, const DecodeCall& call, const DecodeState* state, hipStream_t st) {
   const int V = m->cfg.n_vocab, K = call.beam_k, ts0 = m->ts0();
+  const uint32_t* sup = state ? m->sup_mask : m->sup_mask0;
   if (call.ts)
     WA_HIP(launch_beam_topk_rules(g.logits, g.nb, V, V, K + 1, state ? 0 : 1, state ? kMinTokens : 0, call.eot_stop,
-                                  state, g.ts_rules, ts0, m->bm.top_tok, m->bm.top_lp, nullptr, m->range_flag, st));
+                                  state, g.ts_rules, ts0, m->bm.top_tok, m->bm.top_lp, nullptr, m->range_flag, st,
+                                  sup));
   else
     WA_HIP(launch_beam_topk(g.logits, g.nb, V, V, K + 1, state ? 0 : 1, state ? kMinTokens : 0, call.eot_stop, state,
-                            m->bm.top_tok, m->bm.top_lp, m->range_flag, st));
+                            m->bm.top_tok, m->bm.top_lp, m->range_flag, st, sup));
   WA_HIP(launch_beam_select(select_args(m, g, call), g.nb / K, K, call.beam_c, m->cfg.n_text_ctx, st, ts0, V));
   return WQ4_OK;
 }

@@ -62,7 +62,8 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
                                                         int suppress_fixed, int min_tokens, int eot_stop,
                                                         const DecodeState* __restrict__ state,
                                                         int* __restrict__ out_tok, float* __restrict__ out_lp,
-                                                        int* __restrict__ range_flag) {
+                                                        int* __restrict__ range_flag,
+                                                        const uint32_t* __restrict__ sup) {
   __shared__ float sm[4], ss[4];
   __shared__ float cv[2][4];
   __shared__ int ci[2][4];
@@ -78,9 +79,9 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   }
   float m = -INFINITY, s = 0.0f;
   bool bad = false;
-  auto take = [&](float raw, int i) {
+  auto take = [&](float raw, int i, bool listed) {
     bad |= !__builtin_isfinite(raw);
-    const float v = (mask && i == kEOT) ? -INFINITY : raw;
+    const float v = (listed || (mask && i == kEOT)) ? -INFINITY : raw;
     if (v > m) {
       s = s * expf(m - v) + 1.0f;  // m = -inf: s = 0 * 0 + 1
       m = v;
@@ -104,24 +105,32 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
   };
   // kTopLoads groups in flight per thread (clamped addresses: the loads never
   // branch), taken in ascending order: the sums are those of a one-by-one walk
+  // sup (a model with suppress lists; a kernel argument: wave-uniform): a
+  // group's four ids share one mask word, loaded beside the group
   constexpr int kTopLoads = 8;
   for (int c0 = tid; c0 < nvec; c0 += 256 * kTopLoads) {
     float4 x[kTopLoads];
+    uint32_t w[kTopLoads] = {};
 #pragma unroll
     for (int u = 0; u < kTopLoads; ++u) x[u] = load4(4 * min(c0 + 256 * u, nvec - 1));
+    if (sup) {
+#pragma unroll
+      for (int u = 0; u < kTopLoads; ++u) w[u] = sup[min(c0 + 256 * u, nvec - 1) >> 3];
+    }
 #pragma unroll
     for (int u = 0; u < kTopLoads; ++u) {
       const int c = c0 + 256 * u;
       if (c < nvec) {
         const int i0 = 4 * c;
-        take(x[u].x, i0);
-        take(x[u].y, i0 + 1);
-        take(x[u].z, i0 + 2);
-        take(x[u].w, i0 + 3);
+        const uint32_t b4 = w[u] >> (i0 & 31);
+        take(x[u].x, i0, b4 & 1u);
+        take(x[u].y, i0 + 1, b4 & 2u);
+        take(x[u].z, i0 + 2, b4 & 4u);
+        take(x[u].w, i0 + 3, b4 & 8u);
       }
     }
   }
-  if (tail0 + tid < V && tid < 3) take(z[tail0 + tid], tail0 + tid);
+  if (tail0 + tid < V && tid < 3) take(z[tail0 + tid], tail0 + tid, sup_masked(sup, tail0 + tid));
   if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -191,7 +200,8 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
 // one walk would double the 18 list registers instead.  A masked id enters the
 // lists as -inf and leaves as (0, -inf): not a candidate.
 template <class F>
-__device__ __forceinline__ void row_walk(const float* __restrict__ z, int V, int tid, F&& take) {
+__device__ __forceinline__ void row_walk(const float* __restrict__ z, int V, int tid,
+                                         const uint32_t* __restrict__ sup, F&& take) {
   // as beam_topk_kernel: elements go to threads by index alone, the address
   // only picks the load width
   const uintptr_t addr = reinterpret_cast<uintptr_t>(z);
@@ -204,24 +214,31 @@ __device__ __forceinline__ void row_walk(const float* __restrict__ z, int V, int
     }
     return make_float4(z[i0], z[i0 + 1], z[i0 + 2], z[i0 + 3]);
   };
+  // sup: as beam_topk_kernel, one mask word per group of four ids
   constexpr int kTopLoads = 8;
   for (int c0 = tid; c0 < nvec; c0 += 256 * kTopLoads) {
     float4 x[kTopLoads];
+    uint32_t w[kTopLoads] = {};
 #pragma unroll
     for (int u = 0; u < kTopLoads; ++u) x[u] = load4(4 * min(c0 + 256 * u, nvec - 1));
+    if (sup) {
+#pragma unroll
+      for (int u = 0; u < kTopLoads; ++u) w[u] = sup[min(c0 + 256 * u, nvec - 1) >> 3];
+    }
 #pragma unroll
     for (int u = 0; u < kTopLoads; ++u) {
       const int c = c0 + 256 * u;
       if (c < nvec) {
         const int i0 = 4 * c;
-        take(x[u].x, i0);
-        take(x[u].y, i0 + 1);
-        take(x[u].z, i0 + 2);
-        take(x[u].w, i0 + 3);
+        const uint32_t b4 = w[u] >> (i0 & 31);
+        take(x[u].x, i0, b4 & 1u);
+        take(x[u].y, i0 + 1, b4 & 2u);
+        take(x[u].z, i0 + 2, b4 & 4u);
+        take(x[u].w, i0 + 3, b4 & 8u);
       }
     }
   }
-  if (tail0 + tid < V && tid < 3) take(z[tail0 + tid], tail0 + tid);
+  if (tail0 + tid < V && tid < 3) take(z[tail0 + tid], tail0 + tid, sup_masked(sup, tail0 + tid));
 }
 
 __global__ __launch_bounds__(256) void beam_topk_rules_kernel(const float* __restrict__ logits, int64_t ld, int V,
@@ -230,7 +247,8 @@ __global__ __launch_bounds__(256) void beam_topk_rules_kernel(const float* __res
                                                               const TsRule* __restrict__ rules, int ts0,
                                                               int* __restrict__ out_tok, float* __restrict__ out_lp,
                                                               int* __restrict__ out_mass,
-                                                              int* __restrict__ range_flag) {
+                                                              int* __restrict__ range_flag,
+                                                              const uint32_t* __restrict__ sup) {
   __shared__ float pt[4], pm[4], ps[4];  // walk 1: text maximum, timestamp (m, s) per wave
   __shared__ float sm[4], ss[4];
   __shared__ float cv[2][4];
@@ -241,8 +259,8 @@ __global__ __launch_bounds__(256) void beam_topk_rules_kernel(const float* __res
   const int4 rule = *reinterpret_cast<const int4*>(rules + row);
   // ---- walk 1: rule f from the row after masks a-e
   float mt = -INFINITY, mx = -INFINITY, sx = 0.0f;
-  row_walk(z, V, tid, [&](float raw, int i) {
-    if (ts_masked(i, ts0, rule, mask)) return;
+  row_walk(z, V, tid, sup, [&](float raw, int i, bool listed) {
+    if (listed || ts_masked(i, ts0, rule, mask)) return;
     if (i < ts0) {
       mt = fmaxf(mt, raw);
     } else if (raw > mx) {
@@ -282,9 +300,9 @@ __global__ __launch_bounds__(256) void beam_topk_rules_kernel(const float* __res
   }
   float m = -INFINITY, s = 0.0f;
   bool bad = false;
-  row_walk(z, V, tid, [&](float raw, int i) {
+  row_walk(z, V, tid, sup, [&](float raw, int i, bool listed) {
     bad |= !__builtin_isfinite(raw);  // the range flag: the raw logits
-    const float v = (ts_masked(i, ts0, rule, mask) || (mass && i < ts0)) ? -INFINITY : raw;
+    const float v = (listed || ts_masked(i, ts0, rule, mask) || (mass && i < ts0)) ? -INFINITY : raw;
     if (v > m) {
       s = s * expf(m - v) + 1.0f;  // m = -inf: s = 0 * 0 + 1
       m = v;
@@ -468,22 +486,23 @@ __global__ __launch_bounds__(128) void beam_select_kernel(BeamSelect a, int n_cl
 
 hipError_t launch_beam_topk(const float* logits, int rows, int64_t ld, int V, int kp, int suppress_fixed, int min_tokens,
                             int eot_stop, const DecodeState* state, int* out_tok, float* out_lp, int* range_flag,
-                            hipStream_t st) {
+                            hipStream_t st, const uint32_t* sup) {
   if (rows < 1 || V < 16 || ld < V || kp < 2 || kp > kBeamMaxTop || !logits || !out_tok || !out_lp)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(beam_topk_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, kp, suppress_fixed, min_tokens,
-                     eot_stop, state, out_tok, out_lp, range_flag);
+                     eot_stop, state, out_tok, out_lp, range_flag, sup);
   return hipGetLastError();
 }
 
 hipError_t launch_beam_topk_rules(const float* logits, int rows, int64_t ld, int V, int kp, int suppress_fixed,
                                   int min_tokens, int eot_stop, const DecodeState* state, const TsRule* rules, int ts0,
-                                  int* out_tok, float* out_lp, int* out_mass, int* range_flag, hipStream_t st) {
+                                  int* out_tok, float* out_lp, int* out_mass, int* range_flag, hipStream_t st,
+                                  const uint32_t* sup) {
   if (rows < 1 || V < 16 || ld < V || kp < 2 || kp > kBeamMaxTop || !logits || !out_tok || !out_lp || !rules ||
       ts0 <= kEOT || ts0 > V)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(beam_topk_rules_kernel, dim3(rows), dim3(256), 0, st, logits, ld, V, kp, suppress_fixed,
-                     min_tokens, eot_stop, state, rules, ts0, out_tok, out_lp, out_mass, range_flag);
+                     min_tokens, eot_stop, state, rules, ts0, out_tok, out_lp, out_mass, range_flag, sup);
   return hipGetLastError();
 }
 

@@ -21,9 +21,12 @@ constexpr int kBeamMaxTop = kBeamMaxK + 1;
 // state->step + 1 < min_tokens : suppress_fixed, and always when !eot_stop.
 // Larger lp first, equal lp: larger id first.  out_tok / out_lp: [rows][kp].
 // A non-finite raw logit sets *range_flag.  Needs V >= 16.
+// sup (nullable, both launchers): the pick's suppress mask (wa_pick.hpp); its
+// ids are -inf before the online (m, s) and the lists -- under the rules
+// together with masks a-e, before rule f.
 hipError_t launch_beam_topk(const float* logits, int rows, int64_t ld, int V, int kp, int suppress_fixed, int min_tokens,
                             int eot_stop, const DecodeState* state, int* out_tok, float* out_lp, int* range_flag,
-                            hipStream_t st);
+                            hipStream_t st, const uint32_t* sup = nullptr);
 
 // The same under the timestamp rules (wa_transcribe_beam_ex, timestamps): row
 // r's masks a-e from rules[r] (EOT also by the rule above: mask a), rule f
@@ -34,7 +37,8 @@ hipError_t launch_beam_topk(const float* logits, int rows, int64_t ld, int V, in
 // (nullable) [rows]: 1 where rule f fired.  ts0 in (EOT, V].
 hipError_t launch_beam_topk_rules(const float* logits, int rows, int64_t ld, int V, int kp, int suppress_fixed,
                                   int min_tokens, int eot_stop, const DecodeState* state, const TsRule* rules, int ts0,
-                                  int* out_tok, float* out_lp, int* out_mass, int* range_flag, hipStream_t st);
+                                  int* out_tok, float* out_lp, int* out_mass, int* range_flag, hipStream_t st,
+                                  const uint32_t* sup = nullptr);
 
 // Everything beam_select reads and writes, device pointers.  rows = n_clips *
 // K; row clip * K + j is beam j of its clip.

@@ -27,6 +27,54 @@ wq4_status tiled_check(Dev& d, int64_t R, int D, wq4_precision prec, float* out_
   return WQ4_OK;
 }
 
+// The device mask of a check entry's id list (every id in [0, bound)), null
+// for an empty list: the launch of the entry it extends.
+wq4_status sup_upload(Dev& d, const int32_t* ids, int n_ids, int V, int bound, const uint32_t** out) {
+  *out = nullptr;
+  if (n_ids < 0 || (n_ids > 0 && !ids)) return fail(WQ4_EINVAL, "bad id list");
+  for (int i = 0; i < n_ids; ++i)
+    if (ids[i] < 0 || ids[i] >= bound) return fail(WQ4_EINVAL, "suppressed id outside [0, ts0)");
+  if (n_ids == 0) return WQ4_OK;
+  std::vector<uint32_t> words((size_t)sup_mask_words(V));
+  sup_mask_build(ids, n_ids, V, words.data());
+  auto* dev = d.alloc<uint32_t>(words.size());
+  if (!dev) return fail(WQ4_ENOMEM, "allocation failed");
+  WA_HIP(hipMemcpy(dev, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  *out = dev;
+  return WQ4_OK;
+}
+
+// wa_beam_topk_check / wa_beam_topk_rules_check (records non-null) and their
+// form under a list.
+wq4_status beam_topk_check(int device, const float* logits_dev, int n_rows, int V, int kp, int suppress_eot, int step,
+                           int eot_stop, int ts0, const int32_t* records, const int32_t* ids, int n_ids,
+                           int32_t* tok_dev, float* lp_dev, int32_t* mass_dev, int32_t* flag_out) {
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  const uint32_t* sup = nullptr;
+  WA_TRY(sup_upload(d, ids, n_ids, V, ts0 > 0 ? std::min(ts0, V) : V, &sup));
+  auto* flag = d.alloc<int>(1);
+  TsRule* rules = records ? d.alloc<TsRule>(n_rows) : nullptr;
+  DecodeState* st = step >= 0 ? d.alloc<DecodeState>(1) : nullptr;
+  if (!flag || (records && !rules) || (step >= 0 && !st)) return fail(WQ4_ENOMEM, "allocation failed");
+  if (st) {
+    const DecodeState s0{0, 0, step, 0};
+    WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
+  }
+  if (rules) WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
+  WA_HIP(hipMemset(flag, 0, sizeof(int)));
+  if (rules)
+    WA_HIP(launch_beam_topk_rules(logits_dev, n_rows, V, V, kp, suppress_eot, kMinTokens, eot_stop, st, rules, ts0,
+                                  tok_dev, lp_dev, mass_dev, flag, nullptr, sup));
+  else
+    WA_HIP(launch_beam_topk(logits_dev, n_rows, V, V, kp, suppress_eot, kMinTokens, eot_stop, st, tok_dev, lp_dev, flag,
+                            nullptr, sup));
+  int f = 0;
+  WA_HIP(hipMemcpy(&f, flag, sizeof(int), hipMemcpyDeviceToHost));
+  if (flag_out) *flag_out = f;
+  return WQ4_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,24 +221,19 @@ wq4_status wa_beam_topk_check(int device, const float* logits_dev, int n_rows, i
                               int step, int eot_stop, int32_t* tok_dev, float* lp_dev, int32_t* flag_out) {
   if (!logits_dev || !tok_dev || !lp_dev) return fail(WQ4_EINVAL, "null argument");
   if (n_rows < 1 || V < 16 || kp < 2 || kp > kBeamMaxTop) return fail(WQ4_EINVAL, "bad sizes");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  auto* flag = d.alloc<int>(1);
-  DecodeState* st = nullptr;
-  if (step >= 0) {
-    st = d.alloc<DecodeState>(1);
-    if (!st) return fail(WQ4_ENOMEM, "allocation failed");
-    const DecodeState s0{0, 0, step, 0};
-    WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
-  }
-  if (!flag) return fail(WQ4_ENOMEM, "allocation failed");
-  WA_HIP(hipMemset(flag, 0, sizeof(int)));
-  WA_HIP(launch_beam_topk(logits_dev, n_rows, V, V, kp, suppress_eot, kMinTokens, eot_stop, st, tok_dev, lp_dev, flag,
-                          nullptr));
-  int f = 0;
-  WA_HIP(hipMemcpy(&f, flag, sizeof(int), hipMemcpyDeviceToHost));
-  if (flag_out) *flag_out = f;
-  return WQ4_OK;
+  return beam_topk_check(device, logits_dev, n_rows, V, kp, suppress_eot, step, eot_stop, 0, nullptr, nullptr, 0, tok_dev,
+                         lp_dev, nullptr, flag_out);
+}
+
+wq4_status wa_beam_topk_suppress_check(int device, const float* logits_dev, int n_rows, int V, int kp,
+                                       int suppress_eot, int step, int eot_stop, int ts0, const int32_t* ids,
+                                       int n_ids, const int32_t* records, int32_t* tok_dev, float* lp_dev,
+                                       int32_t* mass_dev, int32_t* flag_out) {
+  if (!logits_dev || !tok_dev || !lp_dev) return fail(WQ4_EINVAL, "null argument");
+  if (n_rows < 1 || V < 16 || kp < 2 || kp > kBeamMaxTop || ts0 <= 50257 || ts0 > V)
+    return fail(WQ4_EINVAL, "bad sizes");
+  return beam_topk_check(device, logits_dev, n_rows, V, kp, suppress_eot, step, eot_stop, ts0, records, ids, n_ids,
+                         tok_dev, lp_dev, mass_dev, flag_out);
 }
 
 static_assert(sizeof(DecodeState) == 4 * sizeof(int32_t), "the decode state is 4 int32 at the ABI");
@@ -230,24 +273,8 @@ wq4_status wa_beam_topk_rules_check(int device, const float* logits_dev, int n_r
   if (!logits_dev || !tok_dev || !lp_dev || !records) return fail(WQ4_EINVAL, "null argument");
   if (n_rows < 1 || V < 16 || kp < 2 || kp > kBeamMaxTop || ts0 <= 50257 || ts0 > V)
     return fail(WQ4_EINVAL, "bad sizes");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  auto* flag = d.alloc<int>(1);
-  auto* rules = d.alloc<TsRule>(n_rows);
-  DecodeState* st = step >= 0 ? d.alloc<DecodeState>(1) : nullptr;
-  if (!flag || !rules || (step >= 0 && !st)) return fail(WQ4_ENOMEM, "allocation failed");
-  if (st) {
-    const DecodeState s0{0, 0, step, 0};
-    WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
-  }
-  WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
-  WA_HIP(hipMemset(flag, 0, sizeof(int)));
-  WA_HIP(launch_beam_topk_rules(logits_dev, n_rows, V, V, kp, suppress_eot, kMinTokens, eot_stop, st, rules, ts0,
-                                tok_dev, lp_dev, mass_dev, flag, nullptr));
-  int f = 0;
-  WA_HIP(hipMemcpy(&f, flag, sizeof(int), hipMemcpyDeviceToHost));
-  if (flag_out) *flag_out = f;
-  return WQ4_OK;
+  return beam_topk_check(device, logits_dev, n_rows, V, kp, suppress_eot, step, eot_stop, ts0, records, nullptr, 0,
+                         tok_dev, lp_dev, mass_dev, flag_out);
 }
 
 wq4_status wa_beam_select_rules_check(int device, const int32_t* top_tok_dev, const float* top_lp_dev, float* S_dev,
@@ -381,15 +408,19 @@ wq4_status wa_embed_check(int device, const int32_t* tokens, const float* tok_em
 // wa_logits_argmax_check; with logprob_dev the scored launch of
 // wa_logits_logprob_check; with rules_host (n_clips records) the timestamp
 // launch of wa_logits_timestamp_check; with temperature / seed (host, n_clips
-// each) the sampled launch of wa_logits_sample_check.
+// each) the sampled launch of wa_logits_sample_check; with sup_ids any of them
+// under that list (wa_logits_suppress_check).
 static wq4_status logits_pick_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
                                     int step, wq4_precision prec, int32_t* tok_dev, float* logprob_dev,
                                     float* logits_dev, const TsRule* rules_host = nullptr, int ts0 = 0,
                                     int32_t* mass_dev = nullptr, const float* temperature = nullptr,
-                                    const uint64_t* seed = nullptr) {
+                                    const uint64_t* seed = nullptr, const int32_t* sup_ids = nullptr,
+                                    int n_sup = 0) {
   const int ns = planes(prec);
   WA_HIP(hipSetDevice(device));
   Dev d;
+  const uint32_t* sup = nullptr;
+  WA_TRY(sup_upload(d, sup_ids, n_sup, V, ts0 > 0 ? std::min(ts0, V) : V, &sup));
   auto* emb2 = d.alloc<_Float16>((size_t)emb_tiled_rows(V) * ns * D);
   auto* st = d.alloc<DecodeState>(1);
   const size_t tb = wq4_atiled_bytes(n_clips, D, prec);
@@ -401,6 +432,7 @@ static wq4_status logits_pick_check(int device, const float* hid_dev, const floa
   p.out_lp = logprob_dev;
   p.out_mass = mass_dev;
   p.ts0 = ts0;
+  p.sup = sup;
   if (!emb2 || !st || !ht || !p.scratch || !p.counter) return fail(WQ4_ENOMEM, "allocation failed");
   if (rules_host) {
     auto* rules = d.alloc<TsRule>(n_clips);
@@ -580,6 +612,86 @@ wq4_status wa_row_sample_check(int device, const float* logits_dev, int n_rows, 
   WA_HIP(hipMemcpy(sd, seed, (size_t)n_rows * 8, hipMemcpyHostToDevice));
   WA_HIP(launch_row_pick(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, temp, sd, pick, tok_dev,
                          logprob_dev, mass_dev, nullptr, nullptr));
+  WA_HIP(hipDeviceSynchronize());
+  return WQ4_OK;
+}
+
+// ---- suppress-token lists: the rule on the host, the kernels on caller data --
+wq4_status wa_suppress_check(const int32_t* always, int n_always, const int32_t* first, int n_first, int ts0) {
+  constexpr int kEot = 50257, kMinText = 16;
+  if (n_always < 0 || n_first < 0 || (n_always > 0 && !always) || (n_first > 0 && !first))
+    return fail(WQ4_EINVAL, "bad suppress lists");
+  if (ts0 <= kEot) return fail(WQ4_EINVAL, "ts0 must lie above EOT");
+  std::vector<bool> listed(kEot, false);
+  for (int i = 0; i < n_always; ++i) {
+    if (always[i] < 0 || always[i] >= ts0 || always[i] == kEot)
+      return fail(WQ4_EINVAL, "an `always` id lies outside [0, EOT) and (EOT, ts0)");
+    if (always[i] < kEot) listed[always[i]] = true;
+  }
+  for (int i = 0; i < n_first; ++i) {
+    if (first[i] < 0 || first[i] >= ts0) return fail(WQ4_EINVAL, "a `first` id lies outside [0, ts0)");
+    if (first[i] < kEot) listed[first[i]] = true;
+  }
+  int left = 0;
+  for (int v = 0; v < kEot; ++v) left += listed[v] ? 0 : 1;
+  if (left < kMinText) return fail(WQ4_EINVAL, "the lists leave fewer than 16 text ids");
+  return WQ4_OK;
+}
+
+wq4_status wa_logits_suppress_check(int device, const float* hid_dev, const float* emb_dev, int n_clips, int D, int V,
+                                    int step, wq4_precision prec, const int32_t* ids, int n_ids,
+                                    const float* temperature, const uint64_t* seed, int ts0, const int32_t* records,
+                                    int32_t* tok_dev, float* logprob_dev, int32_t* mass_dev, float* logits_dev) {
+  if (!hid_dev || !emb_dev || !tok_dev || !temperature != !seed) return fail(WQ4_EINVAL, "null argument");
+  if ((records || temperature) && !logprob_dev) return fail(WQ4_EINVAL, "this mode needs logprob_dev");
+  if (n_clips < 1 || n_clips > 32 || V < 1 || ts0 < 1 || ts0 > V || !emb_tiled_supported(D) ||
+      (temperature && (step < 0 || step > 16)))
+    return fail(WQ4_EINVAL, "bad sizes");
+  if (temperature)
+    for (int b = 0; b < n_clips; ++b)
+      if (!(temperature[b] >= 0.0f) || !std::isfinite(temperature[b]))
+        return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  return logits_pick_check(device, hid_dev, emb_dev, n_clips, D, V, step, prec, tok_dev, logprob_dev, logits_dev,
+                           reinterpret_cast<const TsRule*>(records), ts0, mass_dev, temperature, seed, ids, n_ids);
+}
+
+wq4_status wa_row_suppress_check(int device, const float* logits_dev, int n_rows, int V, int suppress_eot, int pick,
+                                 const int32_t* ids, int n_ids, const float* temperature, const uint64_t* seed,
+                                 int ts0, const int32_t* records, int32_t* tok_dev, float* logprob_dev,
+                                 int32_t* mass_dev) {
+  if (!logits_dev || !tok_dev || !temperature != !seed) return fail(WQ4_EINVAL, "null argument");
+  if ((records || temperature) && !logprob_dev) return fail(WQ4_EINVAL, "this mode needs logprob_dev");
+  if (n_rows < 1 || n_rows > 32 || V < 1 || pick < 0 || ts0 < 1 || ts0 > V) return fail(WQ4_EINVAL, "bad sizes");
+  if (temperature)
+    for (int b = 0; b < n_rows; ++b)
+      if (!(temperature[b] >= 0.0f) || !std::isfinite(temperature[b]))
+        return fail(WQ4_EINVAL, "every temperature must be finite and >= 0");
+  WA_HIP(hipSetDevice(device));
+  Dev d;
+  const uint32_t* sup = nullptr;
+  WA_TRY(sup_upload(d, ids, n_ids, V, ts0, &sup));
+  if (!temperature && !records) {  // the plain / scored pick of a stored row
+    WA_HIP(launch_argmax(logits_dev, n_rows, V, 0, V, suppress_eot, tok_dev, 1, nullptr, nullptr, sup));
+    if (logprob_dev)
+      WA_HIP(launch_row_logprob(logits_dev, n_rows, V, 0, V, suppress_eot, 0, nullptr, tok_dev, 1, 0, logprob_dev, 1,
+                                nullptr, sup));
+    WA_HIP(hipDeviceSynchronize());
+    return WQ4_OK;
+  }
+  float* temp = nullptr;
+  uint64_t* sd = nullptr;
+  if (temperature) {
+    temp = d.alloc<float>(n_rows);
+    sd = d.alloc<uint64_t>(n_rows);
+    if (!temp || !sd) return fail(WQ4_ENOMEM, "allocation failed");
+    WA_HIP(hipMemcpy(temp, temperature, (size_t)n_rows * 4, hipMemcpyHostToDevice));
+    WA_HIP(hipMemcpy(sd, seed, (size_t)n_rows * 8, hipMemcpyHostToDevice));
+  }
+  TsRule* rules = records ? d.alloc<TsRule>(n_rows) : nullptr;
+  if (records && !rules) return fail(WQ4_ENOMEM, "allocation failed");
+  if (records) WA_HIP(hipMemcpy(rules, records, (size_t)n_rows * sizeof(TsRule), hipMemcpyHostToDevice));
+  WA_HIP(launch_row_pick(logits_dev, n_rows, V, V, suppress_eot, 0, nullptr, rules, ts0, temp, sd, pick, tok_dev,
+                         logprob_dev, mass_dev, nullptr, nullptr, sup));
   WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }

@@ -79,7 +79,8 @@ bool fused_pick(const DecGroup& g, const DecodeCall& call, int Tq, const DecodeS
 // The fused pick of group g in the call's mode: a scored call (call.score)
 // leaves the pick's log-probability in next_lp, a timestamp one (call.ts)
 // picks under the clips' rule records, a sampled one (call.sample) at their
-// temperatures and seeds.
+// temperatures and seeds; under the model's `always` suppress mask, if it
+// has lists (every pick but a clip's first).
 PickArgs pick_args(const wa_model* m, const DecGroup& g, const DecodeCall& call) {
   PickArgs p{};
   p.scratch = g.lg_scr;
@@ -90,6 +91,7 @@ PickArgs pick_args(const wa_model* m, const DecGroup& g, const DecodeCall& call)
   p.ts0 = m->ts0();
   p.temp = call.sample ? g.smp_temp : nullptr;
   p.seed = call.sample ? g.smp_seed : nullptr;
+  p.sup = m->sup_mask;
   return p;
 }
 
@@ -106,11 +108,12 @@ wq4_status decode_step(wa_model* m, DecGroup& g, const DecodeCall& call, hipStre
   if (fused_pick(g, call, 1, g.state)) return WQ4_OK;
   if (p.temp || p.rules) {  // the sampled (pick step + 1) or timestamp pick over the stored rows
     WA_HIP(launch_row_pick(g.logits, g.nb, V, V, 0, kMinTokens, g.state, p.rules, p.ts0, p.temp, p.seed, 0, g.next_tok,
-                           g.next_lp, nullptr, m->range_flag, st));
+                           g.next_lp, nullptr, m->range_flag, st, p.sup));
   } else {
-    WA_HIP(launch_argmax_step(g.logits, g.nb, V, kMinTokens, g.state, g.next_tok, m->range_flag, st));
+    WA_HIP(launch_argmax_step(g.logits, g.nb, V, kMinTokens, g.state, g.next_tok, m->range_flag, st, p.sup));
     if (call.score)
-      WA_HIP(launch_row_logprob(g.logits, g.nb, V, 0, V, 0, kMinTokens, g.state, g.next_tok, 1, 0, g.next_lp, 1, st));
+      WA_HIP(launch_row_logprob(g.logits, g.nb, V, 0, V, 0, kMinTokens, g.state, g.next_tok, 1, 0, g.next_lp, 1, st,
+                                p.sup));
   }
   return WQ4_OK;
 }
@@ -567,15 +570,16 @@ wq4_status prompt_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipStr
   if (call.sample || call.ts) {
     // pick 0 and its log-probability through the row kernel: under the first
     // pick's rule record (rule e; EOT is masked with the text) or with EOT
-    // suppressed (whisper.rs:97-99)
+    // suppressed (whisper.rs:97-99); the suppress mask of pick 0 is the union
     const PickArgs p = pick_args(m, g, call);
     WA_HIP(launch_row_pick(g.logits, B, c.n_vocab, c.n_vocab, 1, 0, nullptr, p.rules, p.ts0, p.temp, p.seed, 0,
-                           g.next_tok, g.next_lp, nullptr, m->range_flag, st));
+                           g.next_tok, g.next_lp, nullptr, m->range_flag, st, m->sup_mask0));
   } else {
     // first token: EOT suppressed (whisper.rs:97-99)
-    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, g.next_tok, 1, m->range_flag, st));
+    WA_HIP(launch_argmax(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, g.next_tok, 1, m->range_flag, st, m->sup_mask0));
     if (call.score)  // its log-probability over the masked row; step 0's bookkeeping stores it in slot 0
-      WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st));
+      WA_HIP(launch_row_logprob(g.logits, B, c.n_vocab, 0, c.n_vocab, 1, 0, nullptr, g.next_tok, 1, 0, g.next_lp, 1, st,
+                                m->sup_mask0));
   }
   if (call.score) WA_HIP(hipMemsetAsync(g.logprob, 0xFF, (size_t)B * (kMaxTokens + 1) * 4, st));  // all bits set: NaN
   // frozen clips start done, and counted: the loop stops once the live ones emitted EOT

@@ -404,6 +404,29 @@ struct wa_model {
   // (prepare_call: by the first call in that mode, all or nothing)
   bool score_alloc_ok = false, ts_alloc_ok = false, sample_alloc_ok = false;
   int ts0() const { return cfg.no_timestamps_token() + 1; }  // <|0.00|>
+  // Suppress-token lists (wa_model_set_suppress): the caller's ids and the two
+  // device masks of wa::sup_mask_words(n_vocab) words each, `always` and
+  // `always | first` (one allocation, made by the first set and kept); both
+  // null while no list is set.  Every pick kernel takes the mask of its pick:
+  // pick 0 of a clip the union, later picks `always`.
+  std::vector<int32_t> sup_always, sup_first;
+  uint32_t* sup_buf = nullptr;
+  const uint32_t *sup_mask = nullptr, *sup_mask0 = nullptr;
+  // The captured step graphs bake the mask pointers (and with them the
+  // kernels' instantiations) in: a set or a clear drops every one of them.
+  void drop_graphs() {
+    for (auto& g : groups) {
+      if (g.graph) (void)hipGraphExecDestroy(g.graph);
+      g.graph = nullptr;
+      g.graph_key = -1;
+      for (auto& k : g.kept) {
+        if (k.exec) (void)hipGraphExecDestroy(k.exec);
+        k = wa::DecGroup::KeptGraph{};
+      }
+      if (g.beam_graph) (void)hipGraphExecDestroy(g.beam_graph);
+      g.beam_graph = nullptr;
+    }
+  }
   // live kernel timing (wa_profile_*)
   struct Pending {
     hipEvent_t a, b;

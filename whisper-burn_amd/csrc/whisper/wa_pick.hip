@@ -98,7 +98,8 @@ __device__ __forceinline__ bool better(float& bv, int& bi, float v, int i) {
 
 __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ logits, int V, int lo, int hi,
                                                      int suppress_fixed, int min_tokens, const DecodeState* state,
-                                                     int* __restrict__ out, int out_stride, int* __restrict__ range_flag) {
+                                                     int* __restrict__ out, int out_stride, int* __restrict__ range_flag,
+                                                     const uint32_t* __restrict__ sup) {
   __shared__ float sv[4];
   __shared__ int si[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
   for (int i = lo + tid; i < hi; i += 256) {
     float v = lg[i];
     bad |= !__builtin_isfinite(v);
-    if (suppress && i == kEOT) v = -INFINITY;
+    if ((suppress && i == kEOT) || sup_masked(sup, i)) v = -INFINITY;
     better(bv, bi, v, i);
   }
   if (bad && range_flag) *range_flag = 1;  // plain vector store: every writer stores 1
@@ -132,17 +133,26 @@ __global__ __launch_bounds__(256) void argmax_kernel(const float* __restrict__ l
 }
 
 hipError_t launch_argmax(const float* logits, int B, int V, int lo, int hi, int suppress_eot,
-                         int* out_tok, int out_stride, int* range_flag, hipStream_t st) {
+                         int* out_tok, int out_stride, int* range_flag, hipStream_t st, const uint32_t* sup) {
   hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, V, lo, hi, suppress_eot, 0,
-                     (const DecodeState*)nullptr, out_tok, out_stride, range_flag);
+                     (const DecodeState*)nullptr, out_tok, out_stride, range_flag, sup);
   return hipGetLastError();
 }
 
 hipError_t launch_argmax_step(const float* logits, int B, int V, int min_tokens, const DecodeState* state,
-                              int* out_tok, int* range_flag, hipStream_t st) {
+                              int* out_tok, int* range_flag, hipStream_t st, const uint32_t* sup) {
   hipLaunchKernelGGL(argmax_kernel, dim3(B), dim3(256), 0, st, logits, V, 0, V, 0, min_tokens, state, out_tok, 1,
-                     range_flag);
+                     range_flag, sup);
   return hipGetLastError();
+}
+
+// ------------------------------------------------------ suppress masks --
+int64_t sup_mask_words(int V) { return emb_tiled_rows(V) / 32; }
+
+void sup_mask_build(const int32_t* ids, int n, int V, uint32_t* words) {
+  std::fill(words, words + sup_mask_words(V), 0u);
+  for (int i = 0; i < n; ++i)
+    if (ids[i] >= 0 && ids[i] < V) words[ids[i] >> 5] |= 1u << (ids[i] & 31);
 }
 
 // ------------------------------------------------- timestamp rules --
@@ -498,7 +508,11 @@ __host__ __device__ inline int64_t emb_groups16(int V) { return (int64_t)(V + 12
 // (ts_masked) while lg[] is written.  KEYS (sampled transcribes): the pick
 // index of the noise is state->step + 1.  An instantiation reads the members
 // of `pick` its mode needs and no others.
-template <int NS, int SIDES, int SUMS, int KEYS>
+// SUP (a model with suppress lists): the wave's 32 vocabulary rows v0 .. v0 +
+// 31 are word v0 / 32 of pick.sup -- one scalar word load per wave, issued
+// ahead of the chunk loop, and a bit test per value where lg[] is written,
+// ahead of the EOT / rule masks.  SUP = 0 is the kernel without any of it.
+template <int NS, int SIDES, int SUMS, int KEYS, int SUP>
 __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
     const _Float16* __restrict__ htiled, int B, int D, const _Float16* __restrict__ emb2, int V, int min_tokens,
     const DecodeState* __restrict__ state, PickArgs pick, const int* __restrict__ trace_ids,
@@ -554,6 +568,8 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
 #pragma unroll
     for (int i = 0; i < HPT; ++i) *reinterpret_cast<half8*>(smem + (c & 1) * HCH + (i * 256 + tid) * 16) = hr[i];
   };
+  uint32_t supw = 0;  // SUP: the mask bits of ids v0 .. v0 + 31 (word < sup_mask_words(V): v0 < emb_tiled_rows(V))
+  if constexpr (SUP) supw = pick.sup[__builtin_amdgcn_readfirstlane(v0 >> 5)];
   load_h(0);
   load_e(ec, 0);
   store_h(0);
@@ -616,6 +632,9 @@ __global__ __launch_bounds__(256) void logits_argmax_f16_k32_kernel(
         const int n = v0 + vl;
         float v = acc[mt][nt][j] * kLgInv;
         bad |= n < V && 16 * nt + l16 < B && !__builtin_isfinite(v);
+        if constexpr (SUP) {
+          if ((supw >> vl) & 1u) v = -INFINITY;
+        }
         if constexpr (TS) {
           if (n >= V || ts_masked(n, pick.ts0, rule[nt], suppress != 0)) v = -INFINITY;
         } else {
@@ -688,12 +707,17 @@ hipError_t launch_emb_tiled(const float* emb, int V, int D, int ns, _Float16* ou
 int64_t logits_pick_scratch_floats(int V) { return (int64_t)2 * 5 * 32 * logits_argmax_groups(V); }
 
 // The instantiation of a mode (every one has the same argument list):
-// out_lp -> SUMS, rules -> two sides, temp -> KEYS.
+// out_lp -> SUMS, rules -> two sides, temp -> KEYS, sup -> SUP.
+template <int NS, int SUP>
+static auto pick_kernel_mode(const PickArgs& p) -> decltype(&logits_argmax_f16_k32_kernel<NS, 1, 0, 0, SUP>) {
+  if (p.temp)
+    return p.rules ? &logits_argmax_f16_k32_kernel<NS, 2, 1, 1, SUP> : &logits_argmax_f16_k32_kernel<NS, 1, 1, 1, SUP>;
+  if (p.rules) return &logits_argmax_f16_k32_kernel<NS, 2, 1, 0, SUP>;
+  return p.out_lp ? &logits_argmax_f16_k32_kernel<NS, 1, 1, 0, SUP> : &logits_argmax_f16_k32_kernel<NS, 1, 0, 0, SUP>;
+}
 template <int NS>
-static auto pick_kernel_of(const PickArgs& p) -> decltype(&logits_argmax_f16_k32_kernel<NS, 1, 0, 0>) {
-  if (p.temp) return p.rules ? &logits_argmax_f16_k32_kernel<NS, 2, 1, 1> : &logits_argmax_f16_k32_kernel<NS, 1, 1, 1>;
-  if (p.rules) return &logits_argmax_f16_k32_kernel<NS, 2, 1, 0>;
-  return p.out_lp ? &logits_argmax_f16_k32_kernel<NS, 1, 1, 0> : &logits_argmax_f16_k32_kernel<NS, 1, 0, 0>;
+static auto pick_kernel_of(const PickArgs& p) -> decltype(&logits_argmax_f16_k32_kernel<NS, 1, 0, 0, 0>) {
+  return p.sup ? pick_kernel_mode<NS, 1>(p) : pick_kernel_mode<NS, 0>(p);
 }
 
 hipError_t launch_logits_pick(const _Float16* htiled, int B, int D, const _Float16* emb2, int ns, int V,
@@ -724,15 +748,17 @@ __global__ __launch_bounds__(256) void row_logprob_kernel(const float* __restric
                                                           int mask_eot, int min_tokens,
                                                           const DecodeState* __restrict__ mask_state,
                                                           const int* __restrict__ idx, int idx_stride, int fixed_idx,
-                                                          float* __restrict__ out, int out_stride) {
+                                                          float* __restrict__ out, int out_stride,
+                                                          const uint32_t* __restrict__ sup) {
   __shared__ float sm[4];
   __shared__ float ss[4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const float* z = logits + (size_t)b * ld;
   const bool mask = mask_state ? (mask_state->step + 1 < min_tokens) : mask_eot != 0;
+  auto masked = [&](int i) { return (mask && i == kEOT) || sup_masked(sup, i); };
   float m = -INFINITY;
   for (int i = lo + tid; i < hi; i += 256) {
-    const float v = (mask && i == kEOT) ? -INFINITY : z[i];
+    const float v = masked(i) ? -INFINITY : z[i];
     m = fmaxf(m, v);
   }
 #pragma unroll
@@ -743,7 +769,7 @@ __global__ __launch_bounds__(256) void row_logprob_kernel(const float* __restric
   float s = 0.0f;
   if (m > -INFINITY)
     for (int i = lo + tid; i < hi; i += 256) {
-      const float v = (mask && i == kEOT) ? -INFINITY : z[i];
+      const float v = masked(i) ? -INFINITY : z[i];
       s += expf(v - m);
     }
 #pragma unroll
@@ -755,7 +781,7 @@ __global__ __launch_bounds__(256) void row_logprob_kernel(const float* __restric
     const int id = idx ? idx[(size_t)b * idx_stride] : fixed_idx;
     float r = NAN;
     if (id >= lo && id < hi && m > -INFINITY) {
-      const float v = (mask && id == kEOT) ? -INFINITY : z[id];
+      const float v = masked(id) ? -INFINITY : z[id];
       r = (v - m) - logf(s);
     }
     out[(size_t)b * out_stride] = r;
@@ -764,10 +790,10 @@ __global__ __launch_bounds__(256) void row_logprob_kernel(const float* __restric
 
 hipError_t launch_row_logprob(const float* logits, int rows, int64_t ld, int lo, int hi, int mask_eot, int min_tokens,
                               const DecodeState* mask_state, const int* idx, int idx_stride, int fixed_idx, float* out,
-                              int out_stride, hipStream_t st) {
+                              int out_stride, hipStream_t st, const uint32_t* sup) {
   if (rows < 1 || lo < 0 || lo >= hi || hi > ld || !logits || !out) return hipErrorInvalidValue;
   hipLaunchKernelGGL(row_logprob_kernel, dim3(rows), dim3(256), 0, st, logits, ld, lo, hi, mask_eot, min_tokens,
-                     mask_state, idx, idx_stride, fixed_idx, out, out_stride);
+                     mask_state, idx, idx_stride, fixed_idx, out, out_stride, sup);
   return hipGetLastError();
 }
 
@@ -854,7 +880,8 @@ __global__ __launch_bounds__(256) void row_pick_kernel(const float* __restrict__
                                                        const float* __restrict__ temp,
                                                        const uint64_t* __restrict__ seed, int pick_fixed,
                                                        int* __restrict__ out_tok, float* __restrict__ out_lp,
-                                                       int* __restrict__ out_mass, int* __restrict__ range_flag) {
+                                                       int* __restrict__ out_mass, int* __restrict__ range_flag,
+                                                       const uint32_t* __restrict__ sup) {
   __shared__ float sf[KEYS ? 4 : 2][2][4];  // per side and wave: max, sum (KEYS: key, raw logit)
   __shared__ int si[2][4];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -863,7 +890,9 @@ __global__ __launch_bounds__(256) void row_pick_kernel(const float* __restrict__
   const int ts0 = rules ? ts0_rule : V;
   int4 rule = {};
   if (rules) rule = *reinterpret_cast<const int4*>(rules + b);
-  auto masked = [&](int i) { return rules ? ts_masked(i, ts0, rule, suppress) : (suppress && i == kEOT); };
+  auto masked = [&](int i) {
+    return sup_masked(sup, i) || (rules ? ts_masked(i, ts0, rule, suppress) : (suppress && i == kEOT));
+  };
   float T = 0.0f;
   uint64_t nk = 0;
   if constexpr (KEYS) {
@@ -950,15 +979,15 @@ __global__ __launch_bounds__(256) void row_pick_kernel(const float* __restrict__
 hipError_t launch_row_pick(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
                            const DecodeState* state, const TsRule* rules, int ts0, const float* temp,
                            const uint64_t* seed, int pick, int* out_tok, float* out_lp, int* out_mass,
-                           int* range_flag, hipStream_t st) {
+                           int* range_flag, hipStream_t st, const uint32_t* sup) {
   if (rows < 1 || V < 1 || V > ld || !logits || !out_tok || (rules && ts0 < 1) || !temp != !seed || pick < 0)
     return hipErrorInvalidValue;
   if (temp)
     hipLaunchKernelGGL(row_pick_kernel<1>, dim3(rows), dim3(256), 0, st, logits, ld, V, suppress_eot, min_tokens, state,
-                       rules, ts0, temp, seed, pick, out_tok, out_lp, out_mass, range_flag);
+                       rules, ts0, temp, seed, pick, out_tok, out_lp, out_mass, range_flag, sup);
   else
     hipLaunchKernelGGL(row_pick_kernel<0>, dim3(rows), dim3(256), 0, st, logits, ld, V, suppress_eot, min_tokens, state,
-                       rules, ts0, temp, seed, pick, out_tok, out_lp, out_mass, range_flag);
+                       rules, ts0, temp, seed, pick, out_tok, out_lp, out_mass, range_flag, sup);
   return hipGetLastError();
 }
 

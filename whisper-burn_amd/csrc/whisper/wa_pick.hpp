@@ -21,12 +21,26 @@ hipError_t launch_logits(const float* h, int B, int D, long ldh, const float* em
 // range_flag (nullable): set to 1 when a logit of [lo, hi) is not finite --
 // an MFMA operand left the f16-pair range somewhere upstream (the
 // overflow propagates to every logit of the clip); wa_transcribe checks it.
+// sup (nullable, here and in every launcher below): the suppress mask of the
+// pick (next section); its ids count as -inf before anything else.
 hipError_t launch_argmax(const float* logits, int B, int V, int lo, int hi, int suppress_eot, int* out_tok,
-                         int out_stride, int* range_flag, hipStream_t st);
+                         int out_stride, int* range_flag, hipStream_t st, const uint32_t* sup = nullptr);
 // Step-dependent EOT suppression (whisper.rs:120-122) folded into argmax:
 // suppress iff state->step < min_tokens - 1 (state->step already advanced).
 hipError_t launch_argmax_step(const float* logits, int B, int V, int min_tokens, const DecodeState* state,
-                              int* out_tok, int* range_flag, hipStream_t st);
+                              int* out_tok, int* range_flag, hipStream_t st, const uint32_t* sup = nullptr);
+
+// ---- suppress-token lists (wa_model_set_suppress) -------------------------
+// OpenAI Whisper's SuppressTokens / SuppressBlank as a bit mask over the
+// vocabulary: bit (id & 31) of word id >> 5 set = the id reads as -inf in the
+// row a pick or a top-k sees, ahead of the EOT and timestamp masks.  A model
+// holds two, `always` (picks >= 1) and `always | first` (pick 0), each
+// sup_mask_words(V) words: the bits of emb_tiled_rows(V) ids, so the fused
+// kernel's padded rows read in range.  The range flag is raised from the raw
+// logits: a suppressed id that is not finite still counts.
+int64_t sup_mask_words(int V);
+// The mask of `ids` (n of them, each in [0, V)): sup_mask_words(V) words.
+void sup_mask_build(const int32_t* ids, int n, int V, uint32_t* words);
 
 // ---- timestamp decoding (wa_transcribe_timestamps) ----------------------
 // OpenAI Whisper's ApplyTimestampRules, per row, as a record the bookkeeping
@@ -77,6 +91,9 @@ void sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* 
 //   temp    (with seed: device [B], read when the kernel runs) the Gumbel-max
 //           pick at the rows' temperatures; rule f from the raw sums.  Needs
 //           out_lp.
+//   sup     the suppress mask, applied where lg[] is written in every mode: a
+//           wave's 32 vocabulary rows are one mask word.  Null: the
+//           instantiations without the mask, the kernels of a list-free model.
 // Rows >= B of the outputs are not written.
 struct PickArgs {
   float* scratch;  // logits_pick_scratch_floats(V) f32 / u32: the workgroups' candidates
@@ -88,6 +105,7 @@ struct PickArgs {
   int ts0;
   const float* temp;
   const uint64_t* seed;
+  const uint32_t* sup;  // nullable: the `always` suppress mask (the kernel runs picks >= 1 only)
 };
 int logits_argmax_groups(int V);
 // Floats of PickArgs::scratch, sized for the widest mode: [side][array][32]
@@ -116,7 +134,7 @@ hipError_t launch_logits_pick(const _Float16* htiled, int B, int D, const _Float
 hipError_t launch_row_pick(const float* logits, int rows, int64_t ld, int V, int suppress_eot, int min_tokens,
                            const DecodeState* state, const TsRule* rules, int ts0, const float* temp,
                            const uint64_t* seed, int pick, int* out_tok, float* out_lp, int* out_mass,
-                           int* range_flag, hipStream_t st);
+                           int* range_flag, hipStream_t st, const uint32_t* sup = nullptr);
 
 // Log-probability of one entry of stored logit rows (the scores outside the
 // fused kernel: the prompt's pick, no-speech and language probabilities,
@@ -127,7 +145,7 @@ hipError_t launch_row_pick(const float* logits, int rows, int64_t ld, int V, int
 // id outside [lo, hi) gives NaN.
 hipError_t launch_row_logprob(const float* logits, int rows, int64_t ld, int lo, int hi, int mask_eot, int min_tokens,
                               const DecodeState* mask_state, const int* idx, int idx_stride, int fixed_idx, float* out,
-                              int out_stride, hipStream_t st);
+                              int out_stride, hipStream_t st, const uint32_t* sup = nullptr);
 // x[i] = exp(x[i]), i < n.
 hipError_t launch_exp_inplace(float* x, int n, hipStream_t st);
 // dst[i] = src[i * stride], i < n.

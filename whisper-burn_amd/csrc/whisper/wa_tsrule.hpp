@@ -46,4 +46,10 @@ __device__ __forceinline__ bool ts_masked(int id, int ts0, const int4& r, bool s
   return r.x == 0;                                    // text (c, e)
 }
 
+// Whether a suppress mask (wa_pick.hpp; nullable: a kernel argument, the test
+// is wave-uniform) lists `id`.
+__device__ __forceinline__ bool sup_masked(const uint32_t* __restrict__ sup, int id) {
+  return sup && ((sup[id >> 5] >> (id & 31)) & 1u);
+}
+
 }  // namespace wa

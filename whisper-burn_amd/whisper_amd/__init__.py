@@ -306,6 +306,19 @@ def lib() -> ctypes.CDLL:
                   "wa_self_attention_beam_check", "wa_transcribe_beam_ex", "wa_beam_topk_rules_check",
                   "wa_beam_select_rules_check", "wa_self_attention_beam_pad_check"):
             getattr(L, n).restype = c_int
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        L.wa_suppress_check.argtypes = [i32p, c_int, i32p, c_int, c_int]
+        L.wa_model_set_suppress.argtypes = [vp, i32p, c_int, i32p, c_int]
+        L.wa_model_suppress_ids.argtypes = [vp, c_int, i32p, c_int, ctypes.POINTER(c_int)]
+        L.wa_logits_suppress_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, c_int, f32p, u64p,
+                                               c_int, i32p, vp, vp, vp, vp]
+        L.wa_row_suppress_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, i32p, c_int, f32p, u64p, c_int, i32p,
+                                            vp, vp, vp]
+        L.wa_beam_topk_suppress_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, i32p,
+                                                  c_int, i32p, vp, vp, vp, i32p]
+        for n in ("wa_suppress_check", "wa_model_set_suppress", "wa_model_suppress_ids", "wa_logits_suppress_check",
+                  "wa_row_suppress_check", "wa_beam_topk_suppress_check"):
+            getattr(L, n).restype = c_int
         for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
                   "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
                   "wa_last_pipeline_stats", "wa_last_timings", "wa_encode",
@@ -1074,6 +1087,97 @@ def row_sample_check(logits, temperature, seed, pick: int, suppress_eot: bool = 
     return tok, lp, mass
 
 
+def _id_list(ids):
+    a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+    return a, (a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if a.size else None), int(a.size)
+
+
+def suppress_check(always=(), first=(), ts0: int = 50365) -> bool:
+    """Whether the two suppress-token lists are valid for a model whose
+    <|0.00|> is ts0 (wa_suppress_check; host only): `always` ids in [0, EOT) or
+    (EOT, ts0), `first` ids in [0, ts0), at least 16 text ids left."""
+    _a, ap, na = _id_list(always)
+    _f, fp, nf = _id_list(first)
+    return lib().wa_suppress_check(ap, na, fp, nf, int(ts0)) == 0
+
+
+def logits_suppress_check(hid, emb, ids, step: int, ts0: int = 50365, temperature=None, seed=None, histories=None,
+                          max_initial: int = 50, precision: int = wq4.PREC_F16X2, scored: bool = True):
+    """The decode step's fused logits + pick under a suppress list
+    (wa_logits_suppress_check): ids = the list of that pick.  The mode as the
+    entries it extends: greedy (scored False), scored, timestamps (histories),
+    sampled (temperature / seed, histories optional) -> (tokens int32 [B],
+    logprob f32 [B] or None, logits [B, V] as the kernel's masks a-e and the
+    list left them, mass int32 [B] or None).  An empty list returns the bytes of
+    logits_argmax_check / _logprob_ / _timestamp_ / _sample_check."""
+    torch = _torch()
+    B, D = hid.shape
+    V = emb.shape[0]
+    _keep, idp, n_ids = _id_list(ids)
+    sampled = temperature is not None
+    t, s = _sampling_arrays(temperature, seed, B) if sampled else (None, None)
+    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
+    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
+    want_lp = scored or sampled or rec is not None
+    lp = torch.empty(B, device=hid.device, dtype=torch.float32) if want_lp else None
+    mass = torch.zeros(B, device=hid.device, dtype=torch.int32) if rec is not None else None
+    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32)
+    check(lib().wa_logits_suppress_check(
+        _dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step, precision, idp, n_ids,
+        t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if sampled else None,
+        s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if sampled else None, int(ts0),
+        rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None, _ptr(tok),
+        _ptr(lp) if lp is not None else None, _ptr(mass) if mass is not None else None, _ptr(lg)))
+    return tok, lp, lg, mass
+
+
+def row_suppress_check(logits, ids, ts0: int = 50365, suppress_eot: bool = False, pick: int = 0, temperature=None,
+                       seed=None, histories=None, max_initial: int = 50):
+    """The stored-logits picks under a suppress list (wa_row_suppress_check):
+    without temperature and histories the argmax and its log-probability over
+    the masked row, else the timestamp / sampled row pick -> (tokens int32 [R],
+    logprob f32 [R], mass int32 [R] or None)."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    _keep, idp, n_ids = _id_list(ids)
+    sampled = temperature is not None
+    t, s = _sampling_arrays(temperature, seed, R) if sampled else (None, None)
+    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
+    tok = torch.empty(R, device=logits.device, dtype=torch.int32)
+    lp = torch.empty(R, device=logits.device, dtype=torch.float32)
+    mass = torch.zeros(R, device=logits.device, dtype=torch.int32) if (sampled or rec is not None) else None
+    check(lib().wa_row_suppress_check(
+        _dev(logits), _ptr(logits), R, V, 1 if suppress_eot else 0, int(pick), idp, n_ids,
+        t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if sampled else None,
+        s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if sampled else None, int(ts0),
+        rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None, _ptr(tok), _ptr(lp),
+        _ptr(mass) if mass is not None else None))
+    return tok, lp, mass
+
+
+def beam_topk_suppress_check(logits, kp: int, ids, ts0: int = 50365, records=None, step: int = -1,
+                             suppress_eot: bool = False, eot_stop: bool = True):
+    """beam_topk_check (records None) / beam_topk_rules_check under a suppress
+    list (wa_beam_topk_suppress_check) -> (tokens int32 [R, kp],
+    log-probabilities f32 [R, kp], mass int32 [R] or None, range flag)."""
+    torch = _torch()
+    logits = logits.contiguous()
+    R, V = logits.shape
+    _keep, idp, n_ids = _id_list(ids)
+    rec = np.ascontiguousarray(records, np.int32) if records is not None else None
+    assert rec is None or rec.shape == (R, 8)
+    tok = torch.empty((R, kp), device=logits.device, dtype=torch.int32)
+    lp = torch.empty((R, kp), device=logits.device, dtype=torch.float32)
+    mass = torch.empty(R, device=logits.device, dtype=torch.int32) if rec is not None else None
+    flag = ctypes.c_int32(0)
+    check(lib().wa_beam_topk_suppress_check(
+        _dev(logits), _ptr(logits), R, V, kp, 1 if suppress_eot else 0, step, 1 if eot_stop else 0, int(ts0), idp,
+        n_ids, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None, _ptr(tok), _ptr(lp),
+        _ptr(mass) if mass is not None else None, ctypes.byref(flag)))
+    return tok, lp, mass, int(flag.value)
+
+
 def _scored_clip(toks, n, lp, ns, lt, lpr) -> dict:
     """One clip of a scored transcribe: lp its max_tokens + 1 log-probability slots."""
     n = int(n)
@@ -1175,6 +1279,28 @@ class WhisperModel:
 
     def device_bytes(self) -> int:
         return int(lib().wa_model_device_bytes(self._h))
+
+    def set_suppress_tokens(self, always=(), first=()) -> None:
+        """OpenAI's SuppressTokens (`always`: masked at every pick) and
+        SuppressBlank (`first`: masked in addition at a clip's first pick) id
+        lists for every later transcribe of this model (wa_model_set_suppress);
+        two empty lists clear them.  Invalid lists raise WQ4Error and set
+        nothing.  Not to be called while a transcribe runs."""
+        _a, ap, na = _id_list(always)
+        _f, fp, nf = _id_list(first)
+        check(lib().wa_model_set_suppress(self._h, ap, na, fp, nf))
+
+    @property
+    def suppress_tokens(self) -> tuple:
+        """(always, first) as set: two tuples of ids (wa_model_suppress_ids)."""
+        out = []
+        for which in (0, 1):
+            n = ctypes.c_int(0)
+            lib().wa_model_suppress_ids(self._h, which, None, 0, ctypes.byref(n))  # the count
+            buf = (ctypes.c_int32 * max(1, n.value))()
+            check(lib().wa_model_suppress_ids(self._h, which, buf, n.value, ctypes.byref(n)))
+            out.append(tuple(int(buf[i]) for i in range(n.value)))
+        return tuple(out)
 
     def _stream(self):
         return ctypes.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
