@@ -605,8 +605,8 @@ __global__ __launch_bounds__(256) void wv_pack_kernel(const uint8_t* __restrict_
 // weights): the head's 64 outputs go to MTG workgroups (grid z), each staging
 // only its 64 / MTG weight rows and merging the rows' splits itself; every
 // output keeps its wave split and sum order, so its bits do not change.
-template <int NS, int WK, int RPW, int SM, int MTG>
-__global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict__ zpart,
+template <int NS, int WK, int RPW, int SM, int MTG, bool FIT = false>
+__global__ __launch_bounds__(512, FIT ? 4 : 1) void xattn_out_kernel(const float* __restrict__ zpart,
                                                         const float* __restrict__ mlpart, int R, int H, int D, int S,
                                                         const uint8_t* __restrict__ wv,
                                                         const uint32_t* __restrict__ wvp,
@@ -622,6 +622,7 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
   __shared__ __attribute__((aligned(16))) _Float16 zzero[8];
   __shared__ float red[16][64][RPW + 1];
   static_assert(MTG == 1 || WK == kWtQ4, "output groups need the Q4 MFMA projection");
+  static_assert(!FIT || WK == kWtQ4, "the fit form is the Q4 MFMA projection's");
   constexpr int NMT = 4 / MTG;  // 16-output m-tiles per workgroup
   const int h = blockIdx.x, rbase = blockIdx.y * RPW, rstep = 1, mt0 = blockIdx.z * NMT;
   const int tid = threadIdx.x;
@@ -641,8 +642,22 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
       for (int mt = 0; mt < NMT; ++mt) {
         const uint32_t* o = wvp + (((size_t)h * nkb + kb) * 4 + mt0 + mt) * kWvPackU32;
         wq[u][mt] = WA_XATTN_ODIAG == 1 ? 0u : o[l];
-        wd[u][mt] = WA_XATTN_ODIAG == 1 ? 0u : reinterpret_cast<const uint16_t*>(o + 64)[l & 15];
+        if constexpr (!FIT) wd[u][mt] = WA_XATTN_ODIAG == 1 ? 0u : reinterpret_cast<const uint16_t*>(o + 64)[l & 15];
       }
+    }
+  }
+  // FIT: the head's scales go through LDS instead ([kb][m-tile][16] f16, one
+  // or two u32 words per thread in flight, not KPW * NMT registers per lane)
+  constexpr int kWdWords = kMaxD / 32 * NMT * 8, kWdIt = (kWdWords + 511) / 512;
+  __shared__ __attribute__((aligned(4))) uint16_t wds[FIT ? 2 * kWdWords : 2];
+  uint32_t wdr[kWdIt];
+  if constexpr (FIT) {
+#pragma unroll
+    for (int u = 0; u < kWdIt; ++u) {
+      const int i = tid + 512 * u;
+      const int rec = i < nkb * NMT * 8 ? i >> 3 : 0;  // (kb, local m-tile)
+      const uint32_t* o = wvp + (((size_t)h * nkb + rec / NMT) * 4 + mt0 + rec % NMT) * kWvPackU32;
+      wdr[u] = WA_XATTN_ODIAG == 1 ? 0u : o[64 + (i & 7)];
     }
   }
   // merge of the S frame ranges (flash-attention merge, fixed split order):
@@ -660,8 +675,11 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
     const int nq = D / 4;
     constexpr int NIT = (RPW * (kMaxD / 4) + 511) / 512;
     floatx4 zv[NIT][SM];
-#pragma unroll
-    for (int u = 0; u < NIT; ++u) {
+    // FIT: at most kLive items' partials in flight (all of them while they
+    // and the packed Wv fit 128 registers); item u + kLive is fetched once
+    // item u is merged, then the Wv scales.  Same loads, same merge order.
+    constexpr int kLive = !FIT || SM <= 6 || NIT < 2 ? NIT : 2;
+    auto load_item = [&](int u) {
       const int it = tid + 512 * u;
       const int j = it / nq, q = it - j * nq;
       const bool ok = it < RPW * nq && rbase + rstep * j < R;
@@ -673,7 +691,9 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
           zv[u][s] = WA_XATTN_ODIAG == 2         ? floatx4{0.0f, 0.0f, 0.0f, 0.0f}
                      : (WA_XATTN_ZPART_NT & 2) ? __builtin_nontemporal_load(&zp[(size_t)s * H * (D / 4)])
                                                : zp[(size_t)s * H * (D / 4)];
-    }
+    };
+#pragma unroll
+    for (int u = 0; u < kLive; ++u) load_item(u);
     if (tid < RPW) {
       const int j = tid;
       const size_t rb = (size_t)(rbase + rstep * j < R ? rbase + rstep * j : 0) * S;
@@ -696,11 +716,14 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
         }
       swt[j][SM] = lsum;
     }
-    __syncthreads();
+    if constexpr (FIT) {  // issued first, so they land first: the Z loads stay in flight
 #pragma unroll
-    for (int u = 0; u < NIT; ++u) {
+      for (int u = 0; u < kWdIt; ++u)
+        if (tid + 512 * u < nkb * NMT * 8) reinterpret_cast<uint32_t*>(wds)[tid + 512 * u] = wdr[u];
+    }
+    __syncthreads();
+    auto merge_item = [&](int u) {
       const int it = tid + 512 * u;
-      if (it >= RPW * nq) break;
       const int j = it / nq, q = it - j * nq;
       const bool rok = rbase + rstep * j < R;
       floatx4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
@@ -726,6 +749,22 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
       } else {
 #pragma unroll
         for (int e = 0; e < 4; ++e) zs[(4 * q + e) * RPW + j] = rok ? acc[e] / lsum : 0.0f;
+      }
+    };
+    if constexpr (FIT) {
+#pragma unroll
+      for (int u = 0; u < NIT; ++u) {
+        if (tid + 512 * u < RPW * nq) merge_item(u);
+        // the late loads sit outside the branch and are pinned behind the merge
+        __builtin_amdgcn_sched_barrier(0);
+        if (u + kLive < NIT) load_item(u + kLive);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < NIT; ++u) {
+        if (tid + 512 * u >= RPW * nq) break;
+        merge_item(u);
       }
     }
   }
@@ -754,7 +793,8 @@ __global__ __launch_bounds__(512) void xattn_out_kernel(const float* __restrict_
       const half8 bl = *reinterpret_cast<const half8*>(zlp);
 #pragma unroll
       for (int mt = 0; mt < NMT; ++mt) {  // local m-tile: outputs 16 (mt0 + mt) ..
-        const _Float16 d = __builtin_bit_cast(_Float16, (uint16_t)wd[u][mt]) * (_Float16)kWvScale;  // exact: d < 16
+        const uint16_t dbits = FIT ? wds[(kb * NMT + mt) * 16 + n] : (uint16_t)wd[u][mt];
+        const _Float16 d = __builtin_bit_cast(_Float16, dbits) * (_Float16)kWvScale;  // exact: d < 16
         const half2v off = {(_Float16)1032.0f, (_Float16)1032.0f};
         const half2v dv = {d, d};
         half8 ah, al;
@@ -1127,6 +1167,34 @@ void launch_out_rpw(int R, int H, const float* z, const float* ml, int D, int S,
                     const uint32_t* wvp, const float* bv, _Float16* tiled, float* out32, hipStream_t st,
                     bool split_outputs) {
   const dim3 go(H, (R + RPW - 1) / RPW);
+  // Q4 weights, 4 rows: the fit form (at most 128 registers: two workgroups
+  // per CU beside another group's main), its split maximum SM the smallest
+  // instantiated one >= S.  Plans of up to 6 splits -- the pair's and the
+  // triple's 5 and 6 -- are the ones xattn_plan sizes to leave peers their
+  // CUs, so they take it; with 7 or 8 splits a main takes every CU and the
+  // chain runs in turn with it, so the one-per-CU form below stays.
+  // WA_XATTN_OUT_FORM (A/B runs and tests only, read at every launch): 0 =
+  // one per CU, another value = fit, at every S; both give the same bits.
+  if constexpr (WK == kWtQ4 && RPW == 4 && kXattnSplits == 8) {
+    const char* e = getenv("WA_XATTN_OUT_FORM");
+    if (e ? atoi(e) != 0 : S <= 6) {
+#define WA_XOUT_FIT(SM_, MTG_, GRID_)                                                                        \
+  hipLaunchKernelGGL((xattn_out_kernel<NS, WK, RPW, SM_, MTG_, true>), GRID_, dim3(512), 0, st, z, ml, R, H, D, S, wv, \
+                     wvp, bv, tiled, out32)
+      const dim3 g4(go.x, go.y, 4);
+      if (split_outputs) {
+        if (S <= 5) WA_XOUT_FIT(5, 4, g4);
+        else if (S <= 6) WA_XOUT_FIT(6, 4, g4);
+        else WA_XOUT_FIT(8, 4, g4);
+      } else {
+        if (S <= 5) WA_XOUT_FIT(5, 1, go);
+        else if (S <= 6) WA_XOUT_FIT(6, 1, go);
+        else WA_XOUT_FIT(8, 1, go);
+      }
+#undef WA_XOUT_FIT
+      return;
+    }
+  }
   if constexpr (WK == kWtQ4) {
     if (split_outputs) {  // few rows: 4 workgroups per head
       hipLaunchKernelGGL((xattn_out_kernel<NS, WK, RPW, kXattnSplits, 4>), dim3(go.x, go.y, 4), dim3(512), 0, st, z,

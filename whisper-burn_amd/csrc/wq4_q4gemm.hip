@@ -401,13 +401,22 @@ __device__ __forceinline__ unsigned long long dstamp_cyc() {
 #ifndef WQ4_DECODE_BS
 #define WQ4_DECODE_BS 1
 #endif
-template <int NS, int EPI, int PER, int MT, int W, int WK, bool LNA = false>
-__global__ __launch_bounds__(64 * W) void q4_gemm_decode_kernel(const uint8_t* __restrict__ nib,
-                                                              const uint32_t* __restrict__ sc,
-                                                              const float* __restrict__ colscale,
-                                                              const _Float16* __restrict__ at, int mt0, int nbp, int ks,
-                                                              int chunk, float* __restrict__ part,
-                                                              int* __restrict__ counters, EpiArgs e) {
+// FIT (8-wave Q4 f16x2 plans, A-tiled operand): the same arithmetic in at
+// most 128 registers, so that two workgroups share a CU (DESIGN.md section
+// 10, "chain fit").  The weight stream stays all in flight; of the
+// L2-resident A fragments only kFitDepth Q4 blocks are, and block j + kFitDepth
+// is fetched once block j's MFMAs have issued.
+constexpr int kFitDepth = 3;
+template <int NS, int EPI, int PER, int MT, int W, int WK, bool LNA = false, bool FIT = false>
+__global__ __launch_bounds__(64 * W, FIT ? 4 : 1) void q4_gemm_decode_kernel(const uint8_t* __restrict__ nib,
+                                                                           const uint32_t* __restrict__ sc,
+                                                                           const float* __restrict__ colscale,
+                                                                           const _Float16* __restrict__ at, int mt0,
+                                                                           int nbp, int ks, int chunk,
+                                                                           float* __restrict__ part,
+                                                                           int* __restrict__ counters, EpiArgs e) {
+  static_assert(!FIT || (W == 8 && MT == 1 && !LNA && NS == 2 && WK == kWeightsQ4 && WQ4_DECODE_BS),
+                "the fit form: 8-wave Q4 f16x2 plans on the A-tiled operand");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   constexpr int mtiles = MT;
   constexpr int kRedWaves = W == 8 ? W : W - 1;
@@ -580,6 +589,18 @@ __global__ __launch_bounds__(64 * W) void q4_gemm_decode_kernel(const uint8_t* _
       const __amdgpu_buffer_rsrc_t ra = brsrc(reinterpret_cast<const uint8_t*>(at) + (mt0 + mt) * slab + (size_t)bp0 * 4 * NS * 1024,
                                               (uint32_t)cnt * 4 * NS * 1024);
       const bool row_ok = (mt0 + mt) * 32 + r < e.m;
+      if constexpr (FIT) {  // the first kFitDepth Q4 blocks; the rest in the MFMA loop
+#pragma unroll
+        for (int j = 0; j < kFitDepth && j < 2 * PER; ++j)
+#pragma unroll
+          for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+            for (int q = 0; q < NS; ++q) {
+              const int frag = (j * 2 + kk) * NS + q;
+              a[mt][j >> 1][j & 1][kk][q] = kDiag == 2 ? half8{} : bload_h8<0>(ra, row_ok ? frag * 1024 + lane * 16 : kOob);
+            }
+        continue;
+      }
 #pragma unroll
       for (int i = 0; i < PER; ++i)
 #pragma unroll
@@ -593,6 +614,8 @@ __global__ __launch_bounds__(64 * W) void q4_gemm_decode_kernel(const uint8_t* _
             }
     }
   }
+  // every load above is issued before the statistics merge and the MFMAs
+  if constexpr (FIT) __builtin_amdgcn_sched_barrier(0);
 
   // LayerNorm fold, consumer: the row statistics from its tile statistics
   // (lnf_merge_tiles, wq4_lnmath.hpp)
@@ -630,6 +653,47 @@ __global__ __launch_bounds__(64 * W) void q4_gemm_decode_kernel(const uint8_t* _
     const int jmax = mrows <= 8 ? 4 : mrows <= 16 ? 8 : mrows <= 24 ? 12 : 16;
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
+      if constexpr (FIT) {
+        // the same blocks, MFMAs and scale FMAs as below, one Q4 block at a
+        // time; then block j + kFitDepth's fragments into the registers that
+        // block j's left (branch-free: rows >= M and blocks past cnt read 0)
+        const __amdgpu_buffer_rsrc_t ra =
+            brsrc(reinterpret_cast<const uint8_t*>(at) + (size_t)mt0 * ((size_t)nbp * 4 * NS * 1024) +
+                      (size_t)bp0 * 4 * NS * 1024,
+                  (uint32_t)cnt * 4 * NS * 1024);
+        const bool row_ok = mt0 * 32 + r < e.m;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+          if (kDiag != 1 && i < cnt) {
+            const half8 q0 = deq8(br[i][0][blk * 2 + 0]);
+            const half8 q1 = deq8(br[i][0][blk * 2 + 1]);
+            const float d = (float)__builtin_bit_cast(_Float16, (uint16_t)(blk ? (bs[i] >> 16) : (bs[i] & 0xffffu)));
+            floatx16 t = mfma32(a[mt][i][blk][0][0], q0, floatx16{});
+            t = mfma32(a[mt][i][blk][0][1], q0, t);
+            t = mfma32(a[mt][i][blk][1][0], q1, t);
+            t = mfma32(a[mt][i][blk][1][1], q1, t);
+            floatx16& acc = blk ? acc1 : acc0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+              if (j < jmax) acc[j] = fmaf(t[j], d, acc[j]);
+          }
+          constexpr int kBlks = 2 * PER;
+          const int jn = 2 * i + blk + kFitDepth;
+          if (jn < kBlks) {
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+              for (int q = 0; q < NS; ++q) {
+                const int frag = (jn * 2 + kk) * NS + q;
+                a[mt][jn >> 1][jn & 1][kk][q] =
+                    kDiag == 2 ? half8{} : bload_h8<0>(ra, row_ok ? frag * 1024 + lane * 16 : kOob);
+              }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+        continue;
+      }
       if constexpr (WQ4_DECODE_BS && WK == kWeightsQ4 && NS == 2) {
         if (kDiag != 1 && i < cnt) {
 #pragma unroll
@@ -982,6 +1046,20 @@ hipError_t launch_tile_activations(const float* x, _Float16* at, int M, int K, i
   return hipGetLastError();
 }
 
+// Which form an 8-wave Q4 f16x2 launch of 2 or 3 block pairs per wave takes.
+// The fit form is for the 32-row groups of a decode unit, whose chains run
+// beside another group's main on the CUs it leaves; isolated it is 2-4 %
+// slower (the late A fragments), and groups of up to 16 rows decode with
+// mains that take every CU in turn, so they keep the one-per-CU form
+// (--sequential: 953-958 -> 924-925 RTF with the fit form at every row
+// count).  Both give the same bits.  WQ4_DECODE_FORM (A/B runs and tests
+// only), read at every launch: 0 = one per CU, another value = fit, at every
+// row count.
+static bool decode_fit(int rows) {
+  const char* e = getenv("WQ4_DECODE_FORM");
+  return e ? atoi(e) != 0 : rows > 16;
+}
+
 // Stamp bookkeeping (WQ4_STAMP builds): launch slot -> (N, K, rows).
 static int g_dstamp_next = 0;
 static int g_dstamp_meta[kDStampLaunches][3];
@@ -1025,7 +1103,23 @@ static hipError_t launch_gemm_t(const Q4Geom& g, const uint8_t* nib, const uint3
     // 4-wave plans: m-tiles in launches of <= 2.  Launches on one stream
     // complete in order, so they share the workspace and counters.
     if (p.w == 8) {
+      // Q4 f16x2, 2 or 3 block pairs per wave, more than 16 rows: the fit
+      // form (two workgroups per CU)
+      bool fit = false;
+      if constexpr (NS == 2 && WK == kWeightsQ4 && WQ4_DECODE_BS && !WQ4_STAMP) fit = p.per >= 2 && decode_fit(rows);
       for (int mt0 = 0; mt0 < mreal0; ++mt0) {
+        if constexpr (NS == 2 && WK == kWeightsQ4 && WQ4_DECODE_BS && !WQ4_STAMP) {
+          if (fit) {
+#define WQ4_DECFIT(PER_)                                                                                       \
+  hipLaunchKernelGGL((q4_gemm_decode_kernel<2, EPI, PER_, 1, 8, kWeightsQ4, false, true>), grid, dim3(512),     \
+                     decode_lds_bytes(8), st, nib, sc, cs, at, mt0, (int)g.nbp, p.ks, p.chunk, ws->part,        \
+                     ws->counters, es)
+            if (p.per == 2) WQ4_DECFIT(2);
+            else WQ4_DECFIT(3);
+#undef WQ4_DECFIT
+            continue;
+          }
+        }
         if (p.per == 1) WQ4_DEC(1, 1, 8);
         else if (p.per == 2) WQ4_DEC(2, 1, 8);
         else WQ4_DEC(3, 1, 8);
@@ -1091,6 +1185,10 @@ hipError_t launch_q4_gemm(const Q4Geom& g, const uint8_t* nib, const uint32_t* s
 }
 
 }  // namespace wq4
+
+// The dynamic LDS a decode-kernel launch of `waves` waves asks for (the
+// kernel's metadata holds none of it: tests/test_chain_fit_meta.py).
+extern "C" size_t wq4_diag_decode_lds_bytes(int waves) { return wq4::decode_lds_bytes_all(waves); }
 
 // Timing diagnostics (WQ4_STAMP builds only; returns 0 launches otherwise):
 // copies [launches][kDStampWgs][8] stamps of the 8-wave decode kernel and
