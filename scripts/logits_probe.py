@@ -1,4 +1,4 @@
-"""Standalone decode-step logits + pick (wa_logits_argmax_check) at the
+"""Standalone decode-step logits + pick (wa_logits_pick_check, greedy form) at the
 large-v3 shape, REPS calls, for rocprofv3 --kernel-trace: the kernel's
 duration alone (in the model it shares the chip with the other decode
 group).  B (clips) from the env, default 16 = one of two decode groups."""

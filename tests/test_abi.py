@@ -166,9 +166,11 @@ def test_every_whisper_header_function_is_exported():
 
     import whisper_amd
 
-    text = re.sub(r"/\*.*?\*/", "", open(whisper_amd.HEADER_PATH).read(), flags=re.S)
-    names = sorted(set(re.findall(r"\b(wa_[a-z0-9_]+)\s*\(", text)))
-    assert len(names) >= 20
+    per_header = [set(re.findall(r"\b(wa_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", open(p).read(), flags=re.S)))
+                  for p in (whisper_amd.HEADER_PATH, whisper_amd.CHECKS_HEADER_PATH)]
+    assert all(len(n) >= 20 for n in per_header)
+    assert not per_header[0] & per_header[1], sorted(per_header[0] & per_header[1])  # declared once
+    names = sorted(per_header[0] | per_header[1])
     L = whisper_amd.lib()
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing

@@ -23,7 +23,7 @@ NEW = ("wa_model_set_alignment_heads", "wa_align", "wa_align_words", "wa_align_m
 @pytest.mark.parametrize("name", NEW)
 def test_symbols_exported_and_declared(name):
     assert hasattr(whisper_amd.lib(), name)
-    assert name in open(whisper_amd.HEADER_PATH).read()
+    assert name in open(whisper_amd.HEADER_PATH).read() + open(whisper_amd.CHECKS_HEADER_PATH).read()
 
 
 def test_python_surface():

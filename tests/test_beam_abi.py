@@ -15,7 +15,7 @@ EINVAL = 1
 def test_symbols_are_exported():
     L = whisper_amd.lib()
     for name in ("wa_transcribe_beam", "wa_beam_check", "wa_beam_rank", "wa_beam_topk_check", "wa_beam_select_check",
-                 "wa_self_attention_beam_check"):
+                 "wa_self_attention_check"):
         assert hasattr(L, name), name
 
 

@@ -27,8 +27,7 @@ def test_symbols_are_exported():
     import whisper_amd
 
     L = whisper_amd.lib()
-    for name in ("wa_transcribe_beam_ex", "wa_beam_topk_rules_check", "wa_beam_select_rules_check",
-                 "wa_self_attention_beam_pad_check"):
+    for name in ("wa_transcribe_beam_ex", "wa_beam_topk_check", "wa_beam_select_check", "wa_self_attention_check"):
         assert hasattr(L, name), name
     for name in ("beam_topk_rules_check", "beam_select_rules_check", "self_attention_beam_pad_check", "BeamOptions"):
         assert hasattr(whisper_amd, name), name
@@ -44,11 +43,11 @@ def test_new_entries_reject_null_pointers():
                                    None, None) == EINVAL
     assert L.wa_transcribe_beam_ex(None, None, 1, 50259, 4, 1, ctypes.byref(b), None, None, None, None, None,
                                    None) == EINVAL
-    assert L.wa_beam_topk_rules_check(0, None, 1, V, 2, 0, -1, 1, TS0, None, None, None, None, None) == EINVAL
+    assert L.wa_beam_topk_check(0, None, 1, V, 2, 0, -1, 1, TS0, None, 0, None, None, None, None, None) == EINVAL
     assert "null" in L.wa_last_error().decode()
-    assert L.wa_beam_select_rules_check(0, *([None] * 14), TS0, V, 1, 1, 1, 8) == EINVAL
+    assert L.wa_beam_select_check(0, *([None] * 14), TS0, V, 1, 1, 1, 8) == EINVAL
     assert "null" in L.wa_last_error().decode()
-    assert L.wa_self_attention_beam_pad_check(0, None, None, None, None, None, 1, 6, 448, 4, 0, 0, None) == EINVAL
+    assert L.wa_self_attention_check(0, None, None, None, None, None, 1, 1, 6, 448, 4, 0, 0, None) == EINVAL
     assert "null" in L.wa_last_error().decode()
 
 

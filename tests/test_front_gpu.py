@@ -373,7 +373,7 @@ def test_embed_rejects_bad_arguments(torch):
         tiled = torch.zeros(wq4.lib().wq4_atiled_bytes(4, d, 0), dtype=torch.uint8, device="cuda:0")
         stats = torch.zeros(4 * (d // 16) * 2, device="cuda:0")
         return whisper_amd.lib().wa_embed_check(0, tok.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _p(te), Vv,
-                                                _p(pe), ctx, B, Tq, D, pos0, int(use_state), _p(g), 0, _p(x),
+                                                _p(pe), ctx, B, Tq, D, pos0, int(use_state), None, _p(g), 0, _p(x),
                                                 _p(tiled) if g is not None else None,
                                                 _p(stats) if g is not None else None)
 

@@ -132,7 +132,7 @@ def test_check_entries_reject_bad_arguments_on_the_host():
         tok = np.asarray(tokens, np.int32)
         f = p if fold else None
         return L.wa_embed_check(0, tok.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), p, V, p, ctx, B, Tq, D, pos0, 0,
-                                f, 0, p, f, f)
+                                None, f, 0, p, f, f)
 
     for fold in (False, True):
         assert embed([0, 64, 1, 2], 2, 2, 0, fold=fold) == 1  # token == V

@@ -30,7 +30,7 @@ def parent_key(mode, lane, b0, nb, eot, trace, group_kv, range_tier, splits, q):
 
 def test_exported_declared_and_radices_are_the_products():
     assert hasattr(whisper_amd.lib(), "wa_decode_graph_key_check")
-    assert "wa_decode_graph_key_check" in open(whisper_amd.HEADER_PATH).read()
+    assert "wa_decode_graph_key_check" in open(whisper_amd.CHECKS_HEADER_PATH).read()
     assert whisper_amd.XATTN_SHARE_DEN + 1 == RADIX[-1]
 
 

@@ -18,13 +18,13 @@ i32p = ctypes.POINTER(ctypes.c_int32)
 NEW = ("wa_transcribe_prompted", "wa_transcribe_fallback_prompted", "wa_transcribe_long_prompted",
        "wa_long_result_prompt_len", "wa_long_prompt_window", "wa_long_prompt_next", "wa_prompt_check",
        "wa_prompt_logits_ragged", "wa_self_attention_prefill_check", "wa_cross_attention_prefill_check",
-       "wa_self_attention_pad_check", "wa_embed_pad_check")
+       "wa_self_attention_check", "wa_embed_check")
 
 
 @pytest.mark.parametrize("name", NEW)
 def test_symbols_exported_and_declared(name):
     assert hasattr(whisper_amd.lib(), name)
-    assert name in open(whisper_amd.HEADER_PATH).read()
+    assert name in open(whisper_amd.HEADER_PATH).read() + open(whisper_amd.CHECKS_HEADER_PATH).read()
 
 
 def test_python_surface():

@@ -27,7 +27,7 @@ EINVAL = 1
 V = 51866
 
 NEW = ("wa_transcribe_sampled", "wa_transcribe_batches_sampled", "wa_transcribe_fallback", "wa_sample_noise",
-       "wa_logits_sample_check", "wa_row_sample_check")
+       "wa_logits_pick_check", "wa_row_pick_check")
 
 
 def g_bound(g64):
@@ -38,7 +38,7 @@ def g_bound(g64):
 def test_symbols_exported_and_declared(name):
     L = whisper_amd.lib()
     assert hasattr(L, name)
-    assert name in open(whisper_amd.HEADER_PATH).read()
+    assert name in open(whisper_amd.HEADER_PATH).read() + open(whisper_amd.CHECKS_HEADER_PATH).read()
 
 
 def test_python_surface():

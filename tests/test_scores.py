@@ -13,7 +13,7 @@ import whisper_amd
 
 EINVAL = 1
 
-NEW = ("wa_transcribe_scored", "wa_transcribe_batches_scored", "wa_logits_logprob_check", "wa_row_logprob_check")
+NEW = ("wa_transcribe_scored", "wa_transcribe_batches_scored", "wa_logits_pick_check", "wa_row_logprob_check")
 
 
 def test_wq4_einval_value():
@@ -29,7 +29,7 @@ def test_wq4_einval_value():
 def test_symbols_exported_and_declared(name):
     L = whisper_amd.lib()
     assert hasattr(L, name)
-    assert name in open(whisper_amd.HEADER_PATH).read()
+    assert name in open(whisper_amd.HEADER_PATH).read() + open(whisper_amd.CHECKS_HEADER_PATH).read()
 
 
 def _bufs(n=4096):
@@ -105,14 +105,18 @@ def test_logits_logprob_check_rejects_bad_arguments():
     L = whisper_amd.lib()
     buf = (ctypes.c_float * 64)()
     p = ctypes.c_void_p(ctypes.addressof(buf))
-    f = L.wa_logits_logprob_check
-    ok = dict(hid=p, emb=p, tok=p, lp=p)
-    for null in ("hid", "emb", "tok", "lp"):
+    f = lambda hid, emb, n, D, V, tok, lp: L.wa_logits_pick_check(0, hid, emb, n, D, V, 0, 0, None, 0, None, None, 0,
+                                                                  None, tok, lp, None, None)
+    ok = dict(hid=p, emb=p, tok=p)  # (a null logprob is the greedy form: rejected below with the other modes)
+    for null in ("hid", "emb", "tok"):
         a = dict(ok, **{null: None})
-        assert f(0, a["hid"], a["emb"], 1, 128, 26, 0, 0, a["tok"], a["lp"], None) == EINVAL, null
+        assert f(a["hid"], a["emb"], 1, 128, 26, a["tok"], p) == EINVAL, null
+    rec = (ctypes.c_int32 * 8)()
+    assert L.wa_logits_pick_check(0, p, p, 1, 128, 26, 0, 0, None, 0, None, None, 20, rec, p, None, None,
+                                  None) == EINVAL  # a timestamp pick needs logprob_dev
     for n in (0, -1, 33):
-        assert f(0, p, p, n, 128, 26, 0, 0, p, p, None) == EINVAL, n
-    assert f(0, p, p, 1, 100, 26, 0, 0, p, p, None) == EINVAL  # D not a multiple of 128
+        assert f(p, p, n, 128, 26, p, p) == EINVAL, n
+    assert f(p, p, 1, 100, 26, p, p) == EINVAL  # D not a multiple of 128
 
 
 def test_row_logprob_check_rejects_bad_arguments():

@@ -18,15 +18,15 @@ TS0 = 50365  # Large-V3 / TINY_TEST
 V = 51866
 EOT = 50257
 
-NEW = ("wa_suppress_check", "wa_model_set_suppress", "wa_model_suppress_ids", "wa_logits_suppress_check",
-       "wa_row_suppress_check", "wa_beam_topk_suppress_check")
+NEW = ("wa_suppress_check", "wa_model_set_suppress", "wa_model_suppress_ids", "wa_logits_pick_check",
+       "wa_row_pick_check", "wa_beam_topk_check")
 
 
 @pytest.mark.parametrize("name", NEW)
 def test_symbols_exported_and_declared(name):
     L = whisper_amd.lib()
     assert hasattr(L, name)
-    assert name in open(whisper_amd.HEADER_PATH).read()
+    assert name in open(whisper_amd.HEADER_PATH).read() + open(whisper_amd.CHECKS_HEADER_PATH).read()
 
 
 def test_python_surface():

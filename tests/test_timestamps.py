@@ -21,14 +21,14 @@ V = 51866
 EOT = 50257
 
 NEW = ("wa_transcribe_timestamps", "wa_transcribe_batches_timestamps", "wa_segments_from_tokens",
-       "wa_timestamp_rule", "wa_logits_timestamp_check", "wa_row_timestamp_check", "wa_timestamp_bookkeep_check")
+       "wa_timestamp_rule", "wa_logits_pick_check", "wa_row_pick_check", "wa_timestamp_bookkeep_check")
 
 
 @pytest.mark.parametrize("name", NEW)
 def test_symbols_exported_and_declared(name):
     L = whisper_amd.lib()
     assert hasattr(L, name)
-    assert name in open(whisper_amd.HEADER_PATH).read()
+    assert name in open(whisper_amd.HEADER_PATH).read() + open(whisper_amd.CHECKS_HEADER_PATH).read()
 
 
 def test_python_surface():

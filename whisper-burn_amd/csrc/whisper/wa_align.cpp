@@ -1,6 +1,6 @@
 // wa_align.cpp -- token-level alignment (wa_align): the capture hook of the
-// prefill pass (align_layer), the model's alignment buffers, the entries and
-// their check entries.  Kernels: wa_align.hip.
+// prefill pass (align_layer), the model's alignment buffers and the entries.
+// Kernels: wa_align.hip.
 #include <set>
 
 #include "wa_model.hpp"
@@ -64,15 +64,15 @@ struct Events {
   }
 };
 
-// the rows [row0, row0 + N) x [0, F) of a clip's msum [.][fld] -> dst [.][dst_ld], on st
+}  // namespace
+
+namespace wa {
+
+// The rows [row0, row0 + N) x [0, F) of a clip's msum [.][fld] -> dst [.][dst_ld], on st
 hipError_t copy_matrix(const float* msum, int fld, int row0, int N, int F, float* dst, int dst_ld, hipStream_t st) {
   return hipMemcpy2DAsync(dst, (size_t)dst_ld * 4, msum + (size_t)row0 * fld, (size_t)fld * 4, (size_t)F * 4, (size_t)N,
                           hipMemcpyDeviceToDevice, st);
 }
-
-}  // namespace
-
-namespace wa {
 
 wq4_status align_layer(wa_model* m, DecGroup& g, int li, const float* xk, int P, hipStream_t st, bool* done) {
   const Config& c = m->cfg;
@@ -242,74 +242,6 @@ wq4_status wa_align_words(const int32_t* jump, int n_rows, const int32_t* word_l
     bnd += word_len[k];
     end_s[k] = (float)jump[bnd] / 50.0f;
   }
-  return WQ4_OK;
-}
-
-wq4_status wa_align_matrix_check(int device, const float* q_dev, const float* k_dev, int n_clips, int P,
-                                 const int32_t* pad, int T, int H, const int32_t* heads, int n_heads,
-                                 const int32_t* F, int first_row, wq4_precision prec, float* matrix_out_dev) {
-  if (!q_dev || !k_dev || !pad || !heads || !F || !matrix_out_dev) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || P < 1 || P > 448 || T < 4 || H < 1 || n_heads < 1 || first_row < 0)
-    return fail(WQ4_EINVAL, "bad sizes");
-  if (prec != WQ4_PREC_F16X2 && prec != WQ4_PREC_F16) return fail(WQ4_EINVAL, "unknown precision");
-  std::set<int> seen;
-  for (int i = 0; i < n_heads; ++i)
-    if (heads[i] < 0 || heads[i] >= H || !seen.insert(heads[i]).second)
-      return fail(WQ4_EINVAL, "heads must be distinct and in [0, H)");
-  std::vector<int> r0(n_clips), N(n_clips);
-  for (int c = 0; c < n_clips; ++c) {
-    if (pad[c] < 0 || pad[c] >= P) return fail(WQ4_EINVAL, "pad out of range");
-    if (F[c] < 4 || F[c] > T) return fail(WQ4_EINVAL, "F must be in [4, T]");
-    r0[c] = pad[c] + first_row;
-    N[c] = P - pad[c] - 1 - first_row;
-    if (N[c] < 1) return fail(WQ4_EINVAL, "a clip needs at least one row: P - pad - 1 - first_row >= 1");
-  }
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  const int fld = align_fld(T);
-  const size_t rows = (size_t)n_clips * P;
-  float* w = d.alloc<float>((size_t)kAlignHeadsPerPass * rows * fld);
-  float* msum = d.alloc<float>(rows * fld);
-  int* pad_dev = d.alloc<int>(n_clips);
-  int* F_dev = d.alloc<int>(n_clips);
-  int* heads_dev = d.alloc<int>(n_heads);
-  if (!w || !msum || !pad_dev || !F_dev || !heads_dev) return fail(WQ4_ENOMEM, "allocation failed");
-  WA_HIP(hipMemcpy(pad_dev, pad, (size_t)n_clips * 4, hipMemcpyHostToDevice));
-  WA_HIP(hipMemcpy(F_dev, F, (size_t)n_clips * 4, hipMemcpyHostToDevice));
-  WA_HIP(hipMemcpy(heads_dev, heads, (size_t)n_heads * 4, hipMemcpyHostToDevice));
-  WA_HIP(hipMemset(matrix_out_dev, 0, rows * T * 4));
-  const int ns = prec == WQ4_PREC_F16 ? 1 : 2;
-  for (int h0 = 0; h0 < n_heads; h0 += kAlignHeadsPerPass) {
-    const int hp = std::min(kAlignHeadsPerPass, n_heads - h0);
-    WA_HIP(launch_align_weights(q_dev, k_dev, n_clips, P, T, H, pad_dev, F_dev, heads_dev + h0, hp, w, fld, ns, nullptr));
-    WA_HIP(launch_align_filter(w, n_clips, P, pad_dev, F_dev, hp, fld, msum, h0 == 0, h0 + hp == n_heads, n_heads,
-                               nullptr));
-  }
-  for (int c = 0; c < n_clips; ++c)
-    WA_HIP(copy_matrix(msum + (size_t)c * P * fld, fld, r0[c], N[c], F[c], matrix_out_dev + (size_t)c * P * T, T, nullptr));
-  WA_HIP(hipDeviceSynchronize());
-  return WQ4_OK;
-}
-
-wq4_status wa_dtw_check(int device, const float* x_dev, int n_clips, int N_ld, int F_ld, const int32_t* N,
-                        const int32_t* F, int32_t* jump_out_dev, uint8_t* trace_out_dev) {
-  if (!x_dev || !N || !F || !jump_out_dev) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || N_ld < 1 || N_ld > 447 || F_ld < 1) return fail(WQ4_EINVAL, "bad sizes");
-  for (int c = 0; c < n_clips; ++c)
-    if (N[c] < 1 || N[c] > N_ld || F[c] < 1 || F[c] > F_ld) return fail(WQ4_EINVAL, "need 1 <= N <= N_ld, 1 <= F <= F_ld");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  int* N_dev = d.alloc<int>(n_clips);
-  int* F_dev = d.alloc<int>(n_clips);
-  int* r0_dev = d.alloc<int>(n_clips);
-  uint8_t* trace = trace_out_dev ? trace_out_dev : d.alloc<uint8_t>((size_t)n_clips * (N_ld + 1) * (F_ld + 1));
-  if (!N_dev || !F_dev || !r0_dev || !trace) return fail(WQ4_ENOMEM, "allocation failed");
-  WA_HIP(hipMemcpy(N_dev, N, (size_t)n_clips * 4, hipMemcpyHostToDevice));
-  WA_HIP(hipMemcpy(F_dev, F, (size_t)n_clips * 4, hipMemcpyHostToDevice));
-  WA_HIP(hipMemset(r0_dev, 0, (size_t)n_clips * 4));
-  WA_HIP(launch_align_dtw(x_dev, (long)N_ld * F_ld, F_ld, r0_dev, N_dev, F_dev, n_clips, false, trace, N_ld, F_ld,
-                          jump_out_dev, N_ld, nullptr));
-  WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }
 

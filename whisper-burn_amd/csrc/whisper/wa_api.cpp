@@ -144,6 +144,28 @@ wq4_status wa_model_config(const wa_model* m, int32_t* cfg) {
 
 size_t wa_model_device_bytes(const wa_model* m) { return m ? m->bytes : 0; }
 
+// The validity rule of the suppress-token lists (host only).
+wq4_status wa_suppress_check(const int32_t* always, int n_always, const int32_t* first, int n_first, int ts0) {
+  constexpr int kEot = 50257, kMinText = 16;
+  if (n_always < 0 || n_first < 0 || (n_always > 0 && !always) || (n_first > 0 && !first))
+    return fail(WQ4_EINVAL, "bad suppress lists");
+  if (ts0 <= kEot) return fail(WQ4_EINVAL, "ts0 must lie above EOT");
+  std::vector<bool> listed(kEot, false);
+  for (int i = 0; i < n_always; ++i) {
+    if (always[i] < 0 || always[i] >= ts0 || always[i] == kEot)
+      return fail(WQ4_EINVAL, "an `always` id lies outside [0, EOT) and (EOT, ts0)");
+    if (always[i] < kEot) listed[always[i]] = true;
+  }
+  for (int i = 0; i < n_first; ++i) {
+    if (first[i] < 0 || first[i] >= ts0) return fail(WQ4_EINVAL, "a `first` id lies outside [0, ts0)");
+    if (first[i] < kEot) listed[first[i]] = true;
+  }
+  int left = 0;
+  for (int v = 0; v < kEot; ++v) left += listed[v] ? 0 : 1;
+  if (left < kMinText) return fail(WQ4_EINVAL, "the lists leave fewer than 16 text ids");
+  return WQ4_OK;
+}
+
 wq4_status wa_model_set_suppress(wa_model* m, const int32_t* always, int n_always, const int32_t* first, int n_first) {
   if (!m) return fail(WQ4_EINVAL, "null model");
   WA_TRY(wa_suppress_check(always, n_always, first, n_first, m->ts0()));  // host only: nothing is set on failure
@@ -229,6 +251,11 @@ wq4_status wa_prompt_logits(wa_model* m, const int32_t* prompt_dev, int n_clips,
   WA_TRY(decoder_forward(m, g, DecodeCall(), prompt_dev, plen, nullptr, 0, 0, st));
   WA_HIP(hipMemcpyAsync(logits_dev, g.logits, (size_t)n_clips * m->cfg.n_vocab * 4, hipMemcpyDeviceToDevice, st));
   return WQ4_OK;
+}
+
+long long wa_decode_graph_key(const wa_model* m, int group) {
+  if (!m || group < 0 || group >= (int)m->groups.size()) return -1;
+  return m->groups[group].graph_key;
 }
 
 int wa_decode_group_rows(int n_clips) {

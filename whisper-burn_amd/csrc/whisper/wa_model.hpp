@@ -1,7 +1,7 @@
 // wa_model.hpp -- internal: the Whisper model runtime's state (struct
 // wa_model) and what its translation units (wa_weights, wa_forward,
-// wa_transcribe, wa_long, wa_prompt, wa_align, wa_beam, wa_api, wa_checks .cpp) need
-// from one another.
+// wa_transcribe, wa_long, wa_prompt, wa_align, wa_beam, wa_mel, wa_api,
+// wa_checks .cpp) need from one another.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "../../../include/whisper_amd.h"
+#include "../../../include/whisper_amd_checks.h"
 #include "../../../include/wq4.h"
 #include "wa_align.hpp"
 #include "wa_beam.hpp"
@@ -531,9 +531,13 @@ wq4_status prefill_group(wa_model* m, DecGroup& g, const DecodeCall& call, hipSt
 // head-major K, kAlignHeadsPerPass heads at a time.  *done: no later layer has
 // alignment heads.
 wq4_status align_layer(wa_model* m, DecGroup& g, int li, const float* xk, int P, hipStream_t st, bool* done);
+// the rows [row0, row0 + N) x [0, F) of a clip's head mean msum [.][fld] -> dst [.][dst_ld], on st
+hipError_t copy_matrix(const float* msum, int fld, int row0, int N, int F, float* dst, int dst_ld, hipStream_t st);
 
 // ---- wa_transcribe.cpp
 bool bad_temperatures(const float* t, int n);  // one is negative or not finite
+// sizes, in order, of the units a call over NB batches decodes at up to `width` batches at once
+std::vector<int> unit_sizes(int NB, int width);
 // The ladder of wa_transcribe_fallback on checked arguments and a prepared
 // sampled call (wa_long.cpp runs it per round).
 wq4_status transcribe_ladder(wa_model* m, const DecodeCall& call, const float* mel_dev, int n_clips,

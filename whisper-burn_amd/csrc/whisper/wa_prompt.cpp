@@ -1,7 +1,7 @@
 // wa_prompt.cpp -- caller prompts of any length (wa_transcribe_prompted): the
-// prefill pass of a decode group over ragged, right-aligned prompts, its
-// entries and its check entries.  The decode steps after it are
-// wa_forward.cpp's, in the pad forms of the embedding and self-attention.
+// prefill pass of a decode group over ragged, right-aligned prompts, and its
+// entries.  The decode steps after it are wa_forward.cpp's, in the pad forms of
+// the embedding and self-attention.
 #include <cmath>
 
 #include "wa_model.hpp"
@@ -12,33 +12,7 @@ namespace {
 
 constexpr int kSOT = 50258;
 
-int planes(wq4_precision prec) { return prec == WQ4_PREC_F16 ? 1 : 2; }
-
 size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-
-// a host pad array, each in [0, lo_max], on the device
-wq4_status pad_to_device(Dev& d, const int32_t* pad, int n, int lo_max, int** out) {
-  for (int i = 0; i < n; ++i)
-    if (pad[i] < 0 || pad[i] > lo_max) return fail(WQ4_EINVAL, "pad out of range");
-  int* p = d.alloc<int>(n);
-  if (!p) return fail(WQ4_ENOMEM, "allocation failed");
-  WA_HIP(hipMemcpy(p, pad, (size_t)n * 4, hipMemcpyHostToDevice));
-  *out = p;
-  return WQ4_OK;
-}
-
-// `launch` writes R rows of width D as the A-tiled operand; returned as f32 rows
-template <class Launch>
-wq4_status tiled_rows(Dev& d, int64_t R, int D, wq4_precision prec, float* out_dev, Launch launch) {
-  const size_t tb = wq4_atiled_bytes(R, D, prec);
-  auto* tiled = d.alloc<_Float16>(tb / 2);
-  if (!tiled) return fail(WQ4_ENOMEM, "allocation failed");
-  WA_HIP(hipMemset(tiled, 0, tb));
-  WA_HIP(launch(tiled));
-  WA_HIP(launch_untile(tiled, (int)R, D, planes(prec), out_dev, nullptr));
-  WA_HIP(hipDeviceSynchronize());
-  return WQ4_OK;
-}
 
 }  // namespace
 
@@ -325,86 +299,6 @@ wq4_status wa_prompt_logits_ragged(wa_model* m, const wa_prompt* prompt, int n_c
   WA_TRY(prefill_group(m, g, call, st, &P));
   WA_HIP(hipMemcpyAsync(logits_dev, g.logits, (size_t)n_clips * m->cfg.n_vocab * 4, hipMemcpyDeviceToDevice, st));
   WA_HIP(hipStreamSynchronize(st));
-  return WQ4_OK;
-}
-
-// ---- the prefill kernels and the step's pad forms on caller data ---------
-wq4_status wa_self_attention_prefill_check(int device, const float* qkv_dev, float* cache_k_dev, float* cache_v_dev,
-                                           int n_clips, int P, const int32_t* pad, int H, int ctx,
-                                           wq4_precision prec, float* out_dev) {
-  if (!qkv_dev || !cache_k_dev || !cache_v_dev || !pad || !out_dev) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || P < 1 || H < 1 || ctx < 1 || ctx > 448 || P > ctx) return fail(WQ4_EINVAL, "bad sizes");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  int* pad_dev = nullptr;
-  WA_TRY(pad_to_device(d, pad, n_clips, P - 1, &pad_dev));
-  return tiled_rows(d, (int64_t)n_clips * P, 64 * H, prec, out_dev, [&](_Float16* tiled) {
-    return launch_prefill_self_attention(qkv_dev, cache_k_dev, cache_v_dev, n_clips, P, H, ctx, pad_dev, tiled,
-                                         planes(prec), nullptr);
-  });
-}
-
-wq4_status wa_cross_attention_prefill_check(int device, const float* q_dev, const float* k_dev, const float* v_dev,
-                                            int n_clips, int P, int T, int H, wq4_precision prec, float* out_dev) {
-  if (!q_dev || !k_dev || !v_dev || !out_dev) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || P < 1 || T < 1 || H < 1) return fail(WQ4_EINVAL, "bad sizes");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  return tiled_rows(d, (int64_t)n_clips * P, 64 * H, prec, out_dev, [&](_Float16* tiled) {
-    return launch_prefill_cross_attention(q_dev, k_dev, v_dev, n_clips, P, T, H, tiled, planes(prec), nullptr);
-  });
-}
-
-wq4_status wa_self_attention_pad_check(int device, const float* qkv_dev, float* cache_k_dev, float* cache_v_dev,
-                                       int n_clips, int H, int ctx, int kv_len, const int32_t* pad,
-                                       wq4_precision prec, float* out_dev) {
-  if (!qkv_dev || !cache_k_dev || !cache_v_dev || !pad || !out_dev) return fail(WQ4_EINVAL, "null argument");
-  if (n_clips < 1 || H < 1 || ctx < 1 || ctx > 448 || kv_len < 0 || kv_len + 1 > ctx)
-    return fail(WQ4_EINVAL, "bad sizes");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  int* pad_dev = nullptr;
-  WA_TRY(pad_to_device(d, pad, n_clips, kv_len, &pad_dev));
-  return tiled_rows(d, n_clips, 64 * H, prec, out_dev, [&](_Float16* tiled) {
-    return launch_decoder_self_attention(qkv_dev, cache_k_dev, cache_v_dev, n_clips, 1, H, ctx, nullptr, kv_len, tiled,
-                                         planes(prec), nullptr, nullptr, pad_dev);
-  });
-}
-
-wq4_status wa_embed_pad_check(int device, const int32_t* tokens, const float* tok_emb_dev, int V,
-                              const float* pos_emb_dev, int ctx, int B, int Tq, int D, int pos0, int use_state,
-                              const int32_t* pad, const float* gamma_dev, wq4_precision prec, float* x_dev,
-                              void* tiled_dev, float* stats_dev) {
-  if (!tokens || !tok_emb_dev || !pos_emb_dev || !x_dev || !pad) return fail(WQ4_EINVAL, "null argument");
-  if (gamma_dev && (!tiled_dev || !stats_dev)) return fail(WQ4_EINVAL, "gamma needs the operand and statistics outputs");
-  if (B < 1 || Tq < 1 || D < 1 || V < 1 || ctx < 1 || (int64_t)B * Tq > 2147483647LL)
-    return fail(WQ4_EINVAL, "bad sizes");
-  if (gamma_dev && D % 32 != 0) return fail(WQ4_EINVAL, "the folded form needs D % 32 == 0");
-  if (pos0 < 0 || (int64_t)pos0 + Tq > ctx) return fail(WQ4_EINVAL, "need 0 <= pos0 and pos0 + Tq <= ctx");
-  const int R = B * Tq;
-  for (int i = 0; i < R; ++i)
-    if (tokens[i] < 0 || tokens[i] >= V) return fail(WQ4_EINVAL, "token id outside [0, V)");
-  WA_HIP(hipSetDevice(device));
-  Dev d;
-  int* pad_dev = nullptr;
-  WA_TRY(pad_to_device(d, pad, B, pos0, &pad_dev));
-  auto* tok = d.alloc<int>(R);
-  if (!tok) return fail(WQ4_ENOMEM, "allocation failed");
-  WA_HIP(hipMemcpy(tok, tokens, (size_t)R * 4, hipMemcpyHostToDevice));
-  DecodeState* st = nullptr;
-  if (use_state) {  // as wa_embed_check: the host position is then a value no row may use
-    st = d.alloc<DecodeState>(1);
-    if (!st) return fail(WQ4_ENOMEM, "allocation failed");
-    const DecodeState s0{pos0, 0, 0, 0};
-    WA_HIP(hipMemcpy(st, &s0, sizeof(s0), hipMemcpyHostToDevice));
-  }
-  const int pos0_host = use_state ? -1 : pos0;
-  if (gamma_dev)
-    WA_HIP(launch_embed_fold(tok, tok_emb_dev, pos_emb_dev, B, Tq, D, st, pos0_host, x_dev, gamma_dev,
-                             static_cast<_Float16*>(tiled_dev), stats_dev, planes(prec), nullptr, pad_dev));
-  else
-    WA_HIP(launch_embed(tok, tok_emb_dev, pos_emb_dev, B, Tq, D, st, pos0_host, x_dev, nullptr, pad_dev));
-  WA_HIP(hipDeviceSynchronize());
   return WQ4_OK;
 }
 

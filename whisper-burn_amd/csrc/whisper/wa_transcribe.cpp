@@ -88,20 +88,6 @@ int lanes_cap() {
   return cap;
 }
 
-// Sizes of the units a call over NB batches decodes at up to `width` batches
-// at once: widest first, and no lone last batch where taking one batch fewer
-// leaves a unit of two (4 -> 2 + 2, 7 -> 3 + 2 + 2) -- a lone batch of 17 ..
-// 32 clips decodes in two groups of half its rows, the slowest form there is.
-std::vector<int> unit_sizes(int NB, int width) {
-  std::vector<int> sizes;
-  for (int rem = NB; rem > 0; rem -= sizes.back()) {
-    int n = std::min(width, rem);
-    if (rem - n == 1 && n > 2) --n;
-    sizes.push_back(n);
-  }
-  return sizes;
-}
-
 // Decode groups of one run_decode: one per batch of a unit of n > 1 batches, or one batch's groups.
 int unit_groups(int B, int n) { return n > 1 ? n : decode_groups(B); }
 
@@ -570,6 +556,20 @@ wq4_status transcribe_pipelined(wa_model* m, const DecodeCall& call, const float
 
 }  // namespace
 
+// Sizes of the units a call over NB batches decodes at up to `width` batches
+// at once: widest first, and no lone last batch where taking one batch fewer
+// leaves a unit of two (4 -> 2 + 2, 7 -> 3 + 2 + 2) -- a lone batch of 17 ..
+// 32 clips decodes in two groups of half its rows, the slowest form there is.
+std::vector<int> wa::unit_sizes(int NB, int width) {
+  std::vector<int> sizes;
+  for (int rem = NB; rem > 0; rem -= sizes.back()) {
+    int n = std::min(width, rem);
+    if (rem - n == 1 && n > 2) --n;
+    sizes.push_back(n);
+  }
+  return sizes;
+}
+
 bool wa::bad_temperatures(const float* t, int n) {
   for (int i = 0; i < n; ++i)
     if (!(t[i] >= 0.0f) || !std::isfinite(t[i])) return true;
@@ -811,6 +811,14 @@ wq4_status wa_transcribe_fallback(wa_model* m, const float* mel_dev, int n_clips
   return transcribe_ladder(m, call, mel_dev, n_clips, fb, tokens_out, n_tokens_out, scores, rung_out, stream);
 }
 
+wq4_status wa_timestamp_rule(const int32_t* tokens, int n, int ts0, int V, int max_initial, int32_t* record_out) {
+  if (!record_out || n < 0 || (n > 0 && !tokens) || ts0 < 1 || V < ts0) return fail(WQ4_EINVAL, "bad arguments");
+  TsRule r = ts_rule_first(ts0, V, max_initial);
+  for (int i = 0; i < n; ++i) r = ts_rule_next(r, tokens[i], ts0, V);
+  std::memcpy(record_out, &r, sizeof(r));
+  return WQ4_OK;
+}
+
 wq4_status wa_sample_noise(uint64_t seed, int pick, int id0, int n, float* u_out, float* g_out) {
   if (pick < 0 || id0 < 0 || n < 0 || (n > 0 && !u_out && !g_out)) return fail(WQ4_EINVAL, "bad arguments");
   sample_noise(seed, pick, id0, n, u_out, g_out);
@@ -866,15 +874,6 @@ wq4_status wa_last_pipeline_stats(const wa_model* m, float* out) {
 int wa_last_pipeline_pairs(const wa_model* m) { return m ? m->pipe_pairs : 0; }
 
 int wa_last_pipeline_units3(const wa_model* m) { return m ? m->pipe_units3 : 0; }
-
-wq4_status wa_pipeline_unit_sizes(int n_batches, int width, int* sizes, int* n_units) {
-  if (!sizes || !n_units) return fail(WQ4_EINVAL, "null argument");
-  if (n_batches < 1 || width < 1 || width > kMaxLanes) return fail(WQ4_EINVAL, "n_batches >= 1, width in [1, 3]");
-  const std::vector<int> s = unit_sizes(n_batches, width);
-  std::copy(s.begin(), s.end(), sizes);
-  *n_units = (int)s.size();
-  return WQ4_OK;
-}
 
 wq4_status wa_transcribe_trace(wa_model* m, const float* mel_dev, int n_clips, int lang_token, int max_tokens,
                                int eot_stop, int32_t* tokens_out, int32_t* n_tokens_out, const int32_t* trace_ids_dev,

@@ -2,337 +2,29 @@
 
 Mirrors WhisperModel::{new, encode, transcribe} (zerr0o/whisper-burn
 src/model/whisper.rs) over lib/libwhisper_amd.so; every Q4 projection runs in
-lib/libwq4.so.  Loud failure if the native libraries are missing.
+lib/libwq4.so.  Loud failure if the native libraries are missing.  The ctypes
+declarations are _ffi.py's, the kernel check wrappers of the parity tests
+checks.py's; both are re-exported here.
 """
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import Optional
 
 import numpy as np
 
 import wq4
 
-LIB_PATH = os.path.join(os.path.dirname(wq4.LIB_PATH), "libwhisper_amd.so")
-HEADER_PATH = os.path.join(os.path.dirname(wq4.HEADER_PATH), "whisper_amd.h")
+from ._ffi import (CHECKS_HEADER_PATH, HEADER_PATH, LIB_PATH, Beam, BeamOptions, BeamResult, Fallback,  # noqa: F401
+                   LongOptions, LongPrompt, LongSegment, LongWindow, Prompt, Sampling, Scores, Segment, _as, _dev,
+                   _i32, _i64, _ptr, _torch, check, lib)
+from .checks import *  # noqa: F401,F403  -- the check wrappers and probes
+from .checks import _id_list, _sampling_arrays
+
 VARIANTS = {"large_v3": 0, "medium": 1, "tiny_test": 2}
 CFG_KEYS = ["n_mels", "n_audio_ctx", "n_audio_state", "n_audio_head", "n_audio_layer", "n_text_ctx",
             "n_text_state", "n_text_head", "n_text_layer", "n_vocab", "n_lang"]
-_lib: Optional[ctypes.CDLL] = None
-
-
-class Scores(ctypes.Structure):
-    """struct wa_scores: host arrays, each nullable."""
-
-    _fields_ = [("token_logprob", ctypes.POINTER(ctypes.c_float)), ("no_speech_prob", ctypes.POINTER(ctypes.c_float)),
-                ("lang_token", ctypes.POINTER(ctypes.c_int32)), ("lang_prob", ctypes.POINTER(ctypes.c_float))]
-
-
-class Beam(ctypes.Structure):
-    """struct wa_beam: beams per clip, finished sequences kept per clip, length penalty (NaN: none)."""
-
-    _fields_ = [("beam_size", ctypes.c_int), ("max_candidates", ctypes.c_int), ("length_penalty", ctypes.c_float)]
-
-
-class BeamOptions(ctypes.Structure):
-    """struct wa_beam_options: timestamp rules, their max_initial, one caller prompt per clip (nullable)."""
-
-    _fields_ = [("timestamps", ctypes.c_int), ("max_initial", ctypes.c_int), ("prompt", ctypes.c_void_p)]
-
-
-class BeamResult(ctypes.Structure):
-    """struct wa_beam_result: host arrays, each nullable."""
-
-    _fields_ = [("cand_tokens", ctypes.POINTER(ctypes.c_int32)), ("cand_n_tokens", ctypes.POINTER(ctypes.c_int32)),
-                ("cand_sum_logprob", ctypes.POINTER(ctypes.c_float)), ("n_candidates", ctypes.POINTER(ctypes.c_int32)),
-                ("best", ctypes.POINTER(ctypes.c_int32))]
-
-
-class Segment(ctypes.Structure):
-    """struct wa_segment: tokens [tok_begin, tok_end) from start_s to end_s."""
-
-    _fields_ = [("start_s", ctypes.c_float), ("end_s", ctypes.c_float), ("tok_begin", ctypes.c_int32),
-                ("tok_end", ctypes.c_int32)]
-
-
-class Sampling(ctypes.Structure):
-    """struct wa_sampling: per-clip host temperatures and seeds of a sampled transcribe."""
-
-    _fields_ = [("temperature", ctypes.POINTER(ctypes.c_float)), ("seed", ctypes.POINTER(ctypes.c_uint64)),
-                ("timestamps", ctypes.c_int), ("max_initial", ctypes.c_int)]
-
-
-class Fallback(ctypes.Structure):
-    """struct wa_fallback: the temperature ladder, its thresholds and the clips' seeds."""
-
-    _fields_ = [("temperatures", ctypes.POINTER(ctypes.c_float)), ("n_temperatures", ctypes.c_int),
-                ("logprob_threshold", ctypes.c_float), ("no_speech_threshold", ctypes.c_float),
-                ("seed", ctypes.POINTER(ctypes.c_uint64)), ("timestamps", ctypes.c_int),
-                ("max_initial", ctypes.c_int)]
-
-
-class LongOptions(ctypes.Structure):
-    """struct wa_long_options: one transcribe_long call's decode options."""
-
-    _fields_ = [("max_tokens", ctypes.c_int), ("max_windows", ctypes.c_int), ("lang_token", ctypes.c_int),
-                ("max_initial", ctypes.c_int), ("temperatures", ctypes.POINTER(ctypes.c_float)),
-                ("n_temperatures", ctypes.c_int), ("logprob_threshold", ctypes.c_float),
-                ("no_speech_threshold", ctypes.c_float), ("seed", ctypes.POINTER(ctypes.c_uint64))]
-
-
-class LongWindow(ctypes.Structure):
-    """struct wa_long_window: one decoded window of a recording."""
-
-    _fields_ = [(n, ctypes.c_int32) for n in ("stream", "index", "seek", "size", "advance", "skipped", "rung",
-                                               "lang_token", "n_tokens")] + \
-               [(n, ctypes.c_float) for n in ("temperature", "no_speech_prob", "lang_prob")] + \
-               [("avg_logprob", ctypes.c_double)]
-
-
-class LongSegment(ctypes.Structure):
-    """struct wa_long_segment: tokens [tok_begin, tok_end) of a window, in seconds of the recording."""
-
-    _fields_ = [("stream", ctypes.c_int32), ("window", ctypes.c_int32), ("tok_begin", ctypes.c_int32),
-                ("tok_end", ctypes.c_int32), ("start", ctypes.c_double), ("end", ctypes.c_double)]
-
-
-class Prompt(ctypes.Structure):
-    """struct wa_prompt: host prompts [n_clips, ld] and their lengths."""
-
-    _fields_ = [("tokens", ctypes.POINTER(ctypes.c_int32)), ("n_tokens", ctypes.POINTER(ctypes.c_int32)),
-                ("ld", ctypes.c_int)]
-
-
-class LongPrompt(ctypes.Structure):
-    """struct wa_long_prompt: per-recording initial prompts and the conditioning switch."""
-
-    _fields_ = [("initial", ctypes.POINTER(ctypes.c_int32)), ("n_initial", ctypes.POINTER(ctypes.c_int32)),
-                ("ld", ctypes.c_int), ("condition_on_previous_text", ctypes.c_int),
-                ("reset_temperature", ctypes.c_float)]
-
-
 RULE_FIELDS = ("text_ok", "ts_lo", "ts_hi", "first", "last", "penult", "t_last", "pad")  # a rule record's 8 int32
-
-
-def lib() -> ctypes.CDLL:
-    global _lib
-    if _lib is None:
-        wq4.lib()  # libwq4.so first (RTLD_GLOBAL)
-        if not os.path.exists(LIB_PATH):
-            raise wq4.WQ4Error(6, f"{LIB_PATH} not built")
-        L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-        vp, c_int, c_i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        i32p = ctypes.POINTER(ctypes.c_int32)
-        f32p = ctypes.POINTER(ctypes.c_float)
-        L.wa_last_error.restype = ctypes.c_char_p
-        L.wa_model_create_synthetic.argtypes = [c_int, c_int, ctypes.c_uint64, c_int, c_int, ctypes.POINTER(vp)]
-        L.wa_model_destroy.argtypes = [vp]
-        L.wa_model_destroy.restype = None
-        L.wa_model_config.argtypes = [vp, i32p]
-        L.wa_model_device_bytes.argtypes = [vp]
-        L.wa_model_device_bytes.restype = ctypes.c_size_t
-        L.wa_transcribe.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, vp]
-        L.wa_last_timings.argtypes = [vp, f32p]
-        L.wa_transcribe_batches.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, vp]
-        L.wa_last_pipeline_stats.argtypes = [vp, f32p]
-        L.wa_last_pipeline_pairs.argtypes = [vp]
-        L.wa_last_pipeline_pairs.restype = c_int
-        L.wa_last_pipeline_units3.argtypes = [vp]
-        L.wa_last_pipeline_units3.restype = c_int
-        L.wa_pipeline_unit_sizes.argtypes = [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
-        L.wa_pipeline_unit_sizes.restype = c_int
-        L.wa_encode.argtypes = [vp, vp, c_int, vp, vp]
-        L.wa_prompt_logits.argtypes = [vp, vp, c_int, c_int, vp, vp]
-        L.wa_synth_uniform.argtypes = [ctypes.c_uint64, ctypes.c_char_p, c_i64, ctypes.c_float, ctypes.c_float, f32p]
-        L.wa_profile_enable.argtypes = [vp, c_int]
-        L.wa_profile_read.argtypes = [vp, ctypes.POINTER(ctypes.c_double), c_int]
-        L.wa_probe_kernels.argtypes = [vp, c_int, c_int, ctypes.POINTER(ctypes.c_double), c_int]
-        L.wa_decode_group_rows.argtypes = [c_int]
-        L.wa_decode_group_rows.restype = c_int
-        L.wa_model_create_synthetic_ex.argtypes = [c_int, c_int, ctypes.c_uint64, c_int, c_int, c_int,
-                                                   ctypes.POINTER(vp)]
-        L.wa_model_weight_type.argtypes = [vp]
-        L.wa_model_weight_type.restype = c_int
-        L.wa_model_wide_range.argtypes = [vp]
-        L.wa_model_wide_range.restype = c_int
-        L.wa_model_create_from_gguf.argtypes = [c_int, ctypes.c_char_p, c_int, c_int, c_int, ctypes.POINTER(vp)]
-        L.wa_gguf_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
-        L.wa_gguf_close.argtypes = [vp]
-        L.wa_gguf_close.restype = None
-        L.wa_gguf_version.argtypes = [vp]
-        L.wa_gguf_version.restype = c_int
-        L.wa_gguf_tensor_count.argtypes = [vp]
-        L.wa_gguf_tensor_count.restype = c_i64
-        L.wa_gguf_tensor_info.argtypes = [vp, c_i64, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(c_int),
-                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(c_int),
-                                          ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        L.wa_gguf_tensor_data.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t]
-        L.wa_log_mel.argtypes = [c_int, vp, c_int, c_i64, c_i64, c_int, vp, vp]
-        L.wa_mel_filterbank.argtypes = [c_int, f32p, f32p]
-        L.wa_xattn_check.argtypes = [c_int, vp, vp, vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, vp]
-        L.wa_xattn_resident_share.argtypes = [c_int, c_int, c_int, c_int, ctypes.c_double]
-        L.wa_xattn_resident_share.restype = c_int
-        L.wa_xattn_chunk_resident.argtypes = [c_int, c_int]
-        L.wa_xattn_chunk_resident.restype = c_int
-        L.wa_xattn_plan.argtypes = [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
-        L.wa_xattn_plan.restype = c_int
-        L.wa_xattn_plan_splits.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
-        L.wa_xattn_plan_splits.restype = c_int
-        L.wa_decode_graph_key.argtypes = [vp, c_int]
-        L.wa_decode_graph_key.restype = ctypes.c_longlong
-        L.wa_decode_graph_key_check.argtypes = [c_int] * 10
-        L.wa_decode_graph_key_check.restype = ctypes.c_longlong
-        L.wa_xattn_kv_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
-        L.wa_transcribe_trace.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, vp, c_int, vp, vp]
-        L.wa_encoder_attention_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, vp]
-        L.wa_self_attention_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
-        L.wa_logits_argmax_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
-        L.wa_conv_gelu_check.argtypes = [c_int, vp, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_int, vp, vp, vp, c_int,
-                                         vp]
-        L.wa_embed_check.argtypes = [c_int, i32p, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, c_int,
-                                     vp, vp, vp]
-        for n in ("wa_conv_gelu_check", "wa_embed_check"):
-            getattr(L, n).restype = c_int
-        sp =ctypes.POINTER(Scores)
-        L.wa_transcribe_scored.argtypes = [vp, vp, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
-        L.wa_transcribe_batches_scored.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
-        L.wa_logits_logprob_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, vp]
-        L.wa_row_logprob_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, vp, c_int, vp]
-        for n in ("wa_transcribe_scored", "wa_transcribe_batches_scored", "wa_logits_logprob_check",
-                  "wa_row_logprob_check"):
-            getattr(L, n).restype = c_int
-        L.wa_transcribe_timestamps.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, i32p, sp, vp]
-        L.wa_transcribe_batches_timestamps.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, i32p, i32p,
-                                                       sp, vp]
-        L.wa_segments_from_tokens.argtypes = [i32p, c_int, c_int, ctypes.POINTER(Segment), c_int,
-                                              ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
-        L.wa_timestamp_rule.argtypes = [i32p, c_int, c_int, c_int, c_int, i32p]
-        L.wa_logits_timestamp_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, i32p, vp, vp,
-                                                vp, vp]
-        L.wa_row_timestamp_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, i32p, vp, vp, vp]
-        L.wa_timestamp_bookkeep_check.argtypes = [c_int, i32p, c_int, c_int, c_int, c_int, c_int, i32p]
-        for n in ("wa_transcribe_timestamps", "wa_transcribe_batches_timestamps", "wa_segments_from_tokens",
-                  "wa_timestamp_rule", "wa_logits_timestamp_check", "wa_row_timestamp_check",
-                  "wa_timestamp_bookkeep_check"):
-            getattr(L, n).restype = c_int
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        L.wa_transcribe_sampled.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Sampling), i32p, i32p,
-                                            sp, vp]
-        L.wa_transcribe_batches_sampled.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int,
-                                                    ctypes.POINTER(Sampling), i32p, i32p, sp, vp]
-        L.wa_transcribe_fallback.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Fallback), i32p, i32p,
-                                             sp, i32p, vp]
-        L.wa_sample_noise.argtypes = [ctypes.c_uint64, c_int, c_int, c_int, f32p, f32p]
-        L.wa_logits_sample_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, f32p, u64p, c_int, i32p,
-                                             vp, vp, vp, vp]
-        L.wa_row_sample_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, f32p, u64p, c_int, i32p, vp, vp, vp]
-        for n in ("wa_transcribe_sampled", "wa_transcribe_batches_sampled", "wa_transcribe_fallback",
-                  "wa_sample_noise", "wa_logits_sample_check", "wa_row_sample_check"):
-            getattr(L, n).restype = c_int
-        i64p, cip = ctypes.POINTER(c_i64), ctypes.POINTER(c_int)
-        L.wa_long_mel_max.argtypes = [c_int, vp, c_int, i64p, i64p, c_int, vp, vp]
-        L.wa_long_mel_windows.argtypes = [c_int, vp, c_int, i64p, i64p, i32p, i32p, vp, c_int, vp, vp]
-        L.wa_long_advance.argtypes = [i32p, c_int, c_int, c_int, ctypes.c_float, ctypes.c_double, ctypes.c_float,
-                                      ctypes.c_float, cip, cip]
-        L.wa_long_round.argtypes = [i32p, i32p, i32p, c_int, c_int, c_int, cip, cip]
-        L.wa_transcribe_long.argtypes = [vp, vp, c_int, i64p, i64p, ctypes.POINTER(LongOptions), ctypes.POINTER(vp),
-                                         vp]
-        L.wa_long_result_free.argtypes = [vp]
-        L.wa_long_result_free.restype = None
-        L.wa_long_result_streams.argtypes = [vp]
-        L.wa_long_result_max_tokens.argtypes = [vp]
-        L.wa_long_result_stream.argtypes = [vp, c_int, cip, cip, cip]
-        L.wa_long_result_windows.argtypes = [vp, c_int, ctypes.POINTER(LongWindow), c_int, cip]
-        L.wa_long_result_window.argtypes = [vp, c_int, c_int, i32p, c_int, cip, f32p, c_int]
-        L.wa_long_result_segments.argtypes = [vp, c_int, ctypes.POINTER(LongSegment), c_int, cip]
-        for n in ("wa_long_mel_max", "wa_long_mel_windows", "wa_long_advance", "wa_long_round", "wa_transcribe_long",
-                  "wa_long_result_streams", "wa_long_result_max_tokens", "wa_long_result_stream",
-                  "wa_long_result_windows", "wa_long_result_window", "wa_long_result_segments"):
-            getattr(L, n).restype = c_int
-        pp = ctypes.POINTER(Prompt)
-        L.wa_transcribe_prompted.argtypes = [vp, vp, c_int, pp, c_int, c_int, ctypes.POINTER(Sampling), i32p, i32p, sp,
-                                             vp]
-        L.wa_transcribe_fallback_prompted.argtypes = [vp, vp, c_int, pp, c_int, c_int, ctypes.POINTER(Fallback), i32p,
-                                                      i32p, sp, i32p, vp]
-        L.wa_prompt_logits_ragged.argtypes = [vp, pp, c_int, vp, vp]
-        L.wa_prompt_check.argtypes = [pp, c_int, c_int, c_int, c_int]
-        L.wa_prompt_check.restype = c_int
-        L.wa_self_attention_pad_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, i32p, c_int, vp]
-        L.wa_self_attention_prefill_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, i32p, c_int, c_int, c_int, vp]
-        L.wa_cross_attention_prefill_check.argtypes = [c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp]
-        L.wa_embed_pad_check.argtypes = [c_int, i32p, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, i32p,
-                                         vp, c_int, vp, vp, vp]
-        L.wa_transcribe_long_prompted.argtypes = [vp, vp, c_int, i64p, i64p, ctypes.POINTER(LongOptions),
-                                                  ctypes.POINTER(LongPrompt), ctypes.POINTER(vp), vp]
-        L.wa_long_result_prompt_len.argtypes = [vp, c_int, c_int, cip]
-        L.wa_long_prompt_window.argtypes = [i32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, i32p, c_int, cip,
-                                            cip]
-        L.wa_long_prompt_next.argtypes = [i32p, cip, cip, i32p, c_int, c_int, c_int, ctypes.c_float, c_int,
-                                          ctypes.c_float]
-        for n in ("wa_transcribe_prompted", "wa_transcribe_fallback_prompted", "wa_prompt_logits_ragged",
-                  "wa_self_attention_pad_check", "wa_self_attention_prefill_check",
-                  "wa_cross_attention_prefill_check", "wa_embed_pad_check", "wa_transcribe_long_prompted",
-                  "wa_long_result_prompt_len", "wa_long_prompt_window", "wa_long_prompt_next"):
-            getattr(L, n).restype = c_int
-        L.wa_model_set_alignment_heads.argtypes = [vp, i32p, c_int]
-        L.wa_align.argtypes = [vp, vp, c_int, pp, i32p, i32p, i32p, i32p, vp, vp]
-        L.wa_last_align_timings.argtypes = [vp, f32p]
-        L.wa_align_words.argtypes = [i32p, c_int, i32p, c_int, f32p, f32p]
-        L.wa_align_matrix_check.argtypes = [c_int, vp, vp, c_int, c_int, i32p, c_int, c_int, i32p, c_int, i32p, c_int,
-                                            c_int, vp]
-        L.wa_dtw_check.argtypes = [c_int, vp, c_int, c_int, c_int, i32p, i32p, vp, vp]
-        L.wa_alignment_heads_check.argtypes = [i32p, c_int, c_int, c_int]
-        L.wa_align_check.argtypes = [pp, c_int, i32p, i32p, c_int, c_int, c_int]
-        for n in ("wa_model_set_alignment_heads", "wa_align", "wa_last_align_timings", "wa_align_words",
-                  "wa_alignment_heads_check", "wa_align_check",
-                  "wa_align_matrix_check", "wa_dtw_check"):
-            getattr(L, n).restype = c_int
-        L.wa_transcribe_beam.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Beam), i32p, i32p, sp,
-                                         ctypes.POINTER(BeamResult), vp]
-        L.wa_beam_check.argtypes = [ctypes.POINTER(Beam), c_int, c_int]
-        L.wa_beam_rank.argtypes = [f32p, i32p, c_int, ctypes.c_float, i32p]
-        L.wa_beam_topk_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, i32p]
-        L.wa_beam_select_check.argtypes = [c_int] + [vp] * 13 + [c_int] * 4
-        L.wa_self_attention_beam_check.argtypes = [c_int, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp]
-        L.wa_transcribe_beam_ex.argtypes = [vp, vp, c_int, c_int, c_int, c_int, ctypes.POINTER(Beam),
-                                            ctypes.POINTER(BeamOptions), i32p, i32p, sp, ctypes.POINTER(BeamResult), vp]
-        L.wa_beam_topk_rules_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, i32p, vp, vp,
-                                               vp, i32p]
-        L.wa_beam_select_rules_check.argtypes = [c_int] + [vp] * 14 + [c_int] * 6
-        L.wa_self_attention_beam_pad_check.argtypes = [c_int, vp, vp, vp, vp, i32p, c_int, c_int, c_int, c_int, c_int,
-                                                       c_int, vp]
-        for n in ("wa_transcribe_beam", "wa_beam_check", "wa_beam_rank", "wa_beam_topk_check", "wa_beam_select_check",
-                  "wa_self_attention_beam_check", "wa_transcribe_beam_ex", "wa_beam_topk_rules_check",
-                  "wa_beam_select_rules_check", "wa_self_attention_beam_pad_check"):
-            getattr(L, n).restype = c_int
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        L.wa_suppress_check.argtypes = [i32p, c_int, i32p, c_int, c_int]
-        L.wa_model_set_suppress.argtypes = [vp, i32p, c_int, i32p, c_int]
-        L.wa_model_suppress_ids.argtypes = [vp, c_int, i32p, c_int, ctypes.POINTER(c_int)]
-        L.wa_logits_suppress_check.argtypes = [c_int, vp, vp, c_int, c_int, c_int, c_int, c_int, i32p, c_int, f32p, u64p,
-                                               c_int, i32p, vp, vp, vp, vp]
-        L.wa_row_suppress_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, i32p, c_int, f32p, u64p, c_int, i32p,
-                                            vp, vp, vp]
-        L.wa_beam_topk_suppress_check.argtypes = [c_int, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, i32p,
-                                                  c_int, i32p, vp, vp, vp, i32p]
-        for n in ("wa_suppress_check", "wa_model_set_suppress", "wa_model_suppress_ids", "wa_logits_suppress_check",
-                  "wa_row_suppress_check", "wa_beam_topk_suppress_check"):
-            getattr(L, n).restype = c_int
-        for n in ("wa_xattn_check", "wa_xattn_kv_check", "wa_transcribe_trace", "wa_encoder_attention_check", "wa_self_attention_check",
-                  "wa_logits_argmax_check", "wa_log_mel", "wa_mel_filterbank", "wa_model_create_synthetic", "wa_model_config", "wa_transcribe", "wa_transcribe_batches",
-                  "wa_last_pipeline_stats", "wa_last_timings", "wa_encode",
-                  "wa_prompt_logits", "wa_synth_uniform", "wa_profile_enable", "wa_profile_read", "wa_probe_kernels",
-                  "wa_decode_group_rows",
-                  "wa_model_create_from_gguf", "wa_model_create_synthetic_ex", "wa_gguf_open", "wa_gguf_tensor_info", "wa_gguf_tensor_data"):
-            getattr(L, n).restype = c_int
-        _lib = L
-    return _lib
-
-
-def check(st: int) -> None:
-    if st != 0:
-        raise wq4.WQ4Error(st, lib().wa_last_error().decode(errors="replace"))
 
 
 def decode_group_rows(n_clips: int) -> int:
@@ -345,12 +37,6 @@ def synth_uniform(seed: int, name: str, n: int, lo: float, hi: float) -> np.ndar
     out = np.empty(n, np.float32)
     check(lib().wa_synth_uniform(seed, name.encode(), n, lo, hi, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))))
     return out
-
-
-def _torch():
-    import torch
-
-    return torch
 
 
 MEL_FRAMES = 3000
@@ -385,18 +71,6 @@ def log_mel(audio, n_mels: int = 128, n_samples: Optional[int] = None, out=None)
                            ctypes.c_void_p(out.data_ptr()),
                            ctypes.c_void_p(torch.cuda.current_stream(audio.device).cuda_stream)))
     return out
-
-
-def _i64(a):
-    return np.ascontiguousarray(np.asarray(a, np.int64).reshape(-1))
-
-
-def _i32(a):
-    return np.ascontiguousarray(np.asarray(a, np.int32).reshape(-1))
-
-
-def _as(a, ctype):
-    return a.ctypes.data_as(ctypes.POINTER(ctype))
 
 
 def long_mel_max(audio, offset, n_samples, n_mels: int = 128, out=None):
@@ -463,275 +137,6 @@ def long_round(content_frames, seek, windows, max_batch: int, max_windows: int) 
     return [int(out[i]) for i in range(n.value)]
 
 
-def xattn_check(q, wk_raw, wv_raw, bv, enc, Tq: int, H: int, weight_type: int = 0,
-                precision: int = wq4.PREC_F16X2):
-    """One decoder layer's cross-attention through the product kernels
-    (wa_xattn_check): q cuda f32 [B*Tq, 64H], wk_raw / wv_raw cuda uint8 raw
-    weights, bv cuda f32 [64H], enc cuda f32 [B, T, 64H] -> [B*Tq, 64H]."""
-    torch = _torch()
-    B, T, D = enc.shape
-    out = torch.empty((B * Tq, D), device=enc.device, dtype=torch.float32)
-    dev = enc.device.index if enc.device.index is not None else 0
-    ptr = lambda t: ctypes.c_void_p(t.contiguous().data_ptr())
-    check(lib().wa_xattn_check(dev, ptr(q), ptr(wk_raw), ptr(wv_raw), ptr(bv), weight_type, ptr(enc), B, Tq, T, H,
-                               precision, ptr(out)))
-    return out
-
-
-XATTN_SHARE_DEN = 64  # wa_xattn_resident_share counts 64ths of a clip's sub-chunks
-
-
-def xattn_resident_share(live_clips: int, T: int, planes: int, D: int, budget_mb: float = -1.0) -> int:
-    """64ths of every clip's encoder-plane sub-chunks a decode with live_clips
-    clips live keeps in the Infinity Cache (wa_xattn_resident_share; host
-    logic): budget_mb < 0 = the product's rule."""
-    q = int(lib().wa_xattn_resident_share(live_clips, T, planes, D, budget_mb))
-    if q < 0:
-        raise ValueError("bad sizes")
-    return q
-
-
-def xattn_chunk_resident(chunk: int, share: int) -> bool:
-    """Whether 16-frame sub-chunk `chunk` of a clip is resident at `share` 64ths."""
-    r = int(lib().wa_xattn_chunk_resident(chunk, share))
-    if r < 0:
-        raise ValueError("bad chunk / share")
-    return bool(r)
-
-
-def xattn_plan(T: int) -> tuple[int, int]:
-    """(splits, sub-chunks per split) of the cross-attention's frame split for T frames."""
-    s, c = ctypes.c_int(), ctypes.c_int()
-    check(lib().wa_xattn_plan(T, ctypes.byref(s), ctypes.byref(c)))
-    return s.value, c.value
-
-
-def xattn_plan_splits(T: int, rows: int, free_cus: int) -> tuple[int, int]:
-    """(splits, sub-chunks per split) of a decode whose largest group has `rows`
-    rows and whose cross-attention launches may take free_cus CUs (<= 0: no
-    bound): the host rule (wa_xattn_plan_splits), without the
-    WA_XATTN_SPLITS_RT override."""
-    s, c = ctypes.c_int(), ctypes.c_int()
-    check(lib().wa_xattn_plan_splits(T, rows, free_cus, ctypes.byref(s), ctypes.byref(c)))
-    return s.value, c.value
-
-
-def decode_graph_key_check(mode: int, lane: int, b0: int, nb: int, eot: int, trace: int, group_kv: int,
-                           range_tier: int, splits: int, residency: int) -> int:
-    """The step-graph key of these digits, most significant first (mode: scored 1
-    + timestamps 2 + sampled 4); -1 when one is outside its radix
-    (wa_decode_graph_key_check)."""
-    return int(lib().wa_decode_graph_key_check(mode, lane, b0, nb, eot, trace, group_kv, range_tier, splits, residency))
-
-
-def pipeline_unit_sizes(n_batches: int, width: int) -> list[int]:
-    """Sizes, in order, of the units a transcribe_batches over n_batches
-    batches forms when up to `width` batches decode at once: the host rule
-    (wa_pipeline_unit_sizes), without the device's room for lanes."""
-    sizes, n = (ctypes.c_int * max(1, n_batches))(), ctypes.c_int()
-    check(lib().wa_pipeline_unit_sizes(n_batches, width, sizes, ctypes.byref(n)))
-    return [int(sizes[i]) for i in range(n.value)]
-
-
-def xattn_kv_check(q, k, v, Tq: int, precision: int = wq4.PREC_F16X2):
-    """The few-clip cross-attention over cached K / V (wa_xattn_kv_check):
-    q cuda f32 [B*Tq, 64H], k / v cuda f32 head-major [B, H, T, 64] ->
-    [B*Tq, 64H] (softmax(q K^T / 8) V per head)."""
-    torch = _torch()
-    B, H, T, _ = k.shape
-    out = torch.empty((B * Tq, 64 * H), device=k.device, dtype=torch.float32)
-    dev = k.device.index if k.device.index is not None else 0
-    ptr = lambda t: ctypes.c_void_p(t.contiguous().data_ptr())
-    check(lib().wa_xattn_kv_check(dev, ptr(q), ptr(k), ptr(v), B, Tq, T, H, precision, ptr(out)))
-    return out
-
-
-def _dev(t) -> int:
-    return t.device.index if t.device.index is not None else 0
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def encoder_attention_check(qkv, T: int, H: int, precision: int = wq4.PREC_F16X2):
-    """Encoder self-attention through the product kernel (wa_encoder_attention_check):
-    qkv cuda f32 [B*T, 3*64H] -> [B*T, 64H]."""
-    torch = _torch()
-    qkv = qkv.contiguous()
-    B = qkv.shape[0] // T
-    out = torch.empty((B * T, 64 * H), device=qkv.device, dtype=torch.float32)
-    check(lib().wa_encoder_attention_check(_dev(qkv), _ptr(qkv), B, T, H, precision, _ptr(out)))
-    return out
-
-
-def conv_gelu_check(x, w, bias, stride: int, pos=None, out=None):
-    """The conv stem's kernel (wa_conv_gelu_check): x cuda f32 of logical shape
-    [B, C, T_in] in any element strides (x.stride(): channel-major as the mel,
-    or a permuted [B, T_in, C] as conv1's output), w cuda f32 [N, C, 3], bias
-    [N], pos [T_out, N] or None -> [B, T_out, N] = gelu(conv1d(x) + bias)
-    (+ pos), padding 1."""
-    torch = _torch()
-    B, C, T_in = x.shape
-    N = w.shape[0]
-    assert tuple(w.shape) == (N, C, 3)
-    T_out = (T_in - 1) // stride + 1
-    if out is None:
-        out = torch.empty((B, T_out, N), device=x.device, dtype=torch.float32)
-    bs, cs, ts = x.stride()
-    w, bias = w.contiguous(), bias.contiguous()
-    pos = None if pos is None else pos.contiguous()
-    check(lib().wa_conv_gelu_check(_dev(x), _ptr(x), bs, cs, ts, B, C, T_in, stride, _ptr(w), _ptr(bias),
-                                   None if pos is None else _ptr(pos), N, _ptr(out)))
-    return out
-
-
-def embed_check(tokens, tok_emb, pos_emb, B: int, Tq: int, pos0: int, use_state: bool = False, gamma=None,
-                precision: int = wq4.PREC_F16X2, x=None, tiled=None, stats=None):
-    """The decoder's embedding kernels (wa_embed_check): tokens host int32
-    [B * Tq], tok_emb cuda f32 [V, D], pos_emb cuda f32 [ctx, D] -> x
-    [B * Tq, D]; the position reaches the kernel from the host or, with
-    use_state, from a device-resident decode state.  With gamma (cuda f32 [D])
-    the LayerNorm-fold producer form: also (tiled, stats) = the A-tiled operand
-    bytes of x * gamma and the 16-column tile statistics [B * Tq, D / 16, 2].
-    x / tiled / stats: caller-allocated outputs (guarded buffers)."""
-    torch = _torch()
-    V, D = tok_emb.shape
-    ctx = pos_emb.shape[0]
-    tokens = np.ascontiguousarray(tokens, np.int32)
-    assert tokens.size == B * Tq and tok_emb.is_contiguous() and pos_emb.is_contiguous()
-    R = B * Tq
-    if x is None:
-        x = torch.empty((R, D), device=tok_emb.device, dtype=torch.float32)
-    if gamma is not None:
-        if tiled is None:
-            tiled = torch.zeros(wq4.lib().wq4_atiled_bytes(R, D, precision), device=tok_emb.device, dtype=torch.uint8)
-        if stats is None:
-            stats = torch.empty((R, D // 16, 2), device=tok_emb.device, dtype=torch.float32)
-    check(lib().wa_embed_check(_dev(tok_emb), tokens.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(tok_emb), V,
-                               _ptr(pos_emb), ctx, B, Tq, D, pos0, 1 if use_state else 0,
-                               None if gamma is None else _ptr(gamma), precision, _ptr(x),
-                               None if gamma is None else _ptr(tiled), None if gamma is None else _ptr(stats)))
-    return x, tiled, stats
-
-
-def self_attention_check(qkv, cache_k, cache_v, Tq: int, H: int, kv_len: int, precision: int = wq4.PREC_F16X2):
-    """Decoder self-attention through the product kernel (wa_self_attention_check):
-    qkv cuda f32 [B*Tq, 3*64H]; caches [B, H, ctx, 64] (updated in place:
-    the new keys / values appended at kv_len) -> [B*Tq, 64H]."""
-    torch = _torch()
-    B, _, ctx, _ = cache_k.shape
-    out = torch.empty((B * Tq, 64 * H), device=qkv.device, dtype=torch.float32)
-    check(lib().wa_self_attention_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, Tq, H,
-                                        ctx, kv_len, precision, _ptr(out)))
-    return out
-
-
-def self_attention_beam_check(qkv, cache_k, cache_v, anc, H: int, kv_len: int, precision: int = wq4.PREC_F16X2,
-                              f32_out: bool = False):
-    """The beam step's self-attention (wa_self_attention_beam_check): qkv cuda
-    f32 [R, 3*64H]; caches [R, H, ctx, 64] (updated in place: row r's new key /
-    value at (r, kv_len)); anc cuda int32 [R, ctx], key j < kv_len of row r is
-    read from cache row anc[r, j] -> [R, 64H].  anc None: the kernel of
-    self_attention_check itself; f32_out: the f32-row form of range tier 3."""
-    torch = _torch()
-    R, _, ctx, _ = cache_k.shape
-    if anc is not None:
-        assert anc.dtype == torch.int32 and anc.is_contiguous() and tuple(anc.shape) == (R, ctx)
-    out = torch.empty((R, 64 * H), device=qkv.device, dtype=torch.float32)
-    check(lib().wa_self_attention_beam_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v),
-                                             None if anc is None else _ptr(anc), R, H, ctx, kv_len, precision,
-                                             1 if f32_out else 0, _ptr(out)))
-    return out
-
-
-def beam_topk_check(logits, kp: int, step: int = -1, suppress_eot: bool = False, eot_stop: bool = True, tok=None,
-                    lp=None):
-    """The per-row log-softmax + top-kp kernel (wa_beam_topk_check): logits cuda
-    f32 [R, V] -> (tokens int32 [R, kp], log-probabilities f32 [R, kp], range
-    flag).  EOT is masked when not eot_stop, else suppress_eot (step < 0) or
-    step + 1 < 3 through a device state.  tok / lp: output tensors to write
-    into (flat, at least R * kp entries)."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    if tok is None:
-        tok = torch.empty((R, kp), device=logits.device, dtype=torch.int32)
-    if lp is None:
-        lp = torch.empty((R, kp), device=logits.device, dtype=torch.float32)
-    flag = ctypes.c_int32(0)
-    check(lib().wa_beam_topk_check(_dev(logits), _ptr(logits), R, V, kp, 1 if suppress_eot else 0, step,
-                                   1 if eot_stop else 0, _ptr(tok), _ptr(lp), ctypes.byref(flag)))
-    return tok, lp, int(flag.value)
-
-
-BEAM_SELECT_ARRAYS = ("top_tok", "top_lp", "S", "next_tok", "parent", "anc", "fed", "fin_sum", "fin_len", "fin_anc",
-                      "fin_n", "complete", "state")
-
-
-def beam_select_check(arrays: dict, n_clips: int, K: int, C: int, ctx: int) -> None:
-    """One merge step of the beam search in place on the caller's cuda tensors
-    (wa_beam_select_check; BEAM_SELECT_ARRAYS names them, shapes in
-    include/whisper_amd.h): consecutive calls are consecutive steps."""
-    t = [arrays[k] for k in BEAM_SELECT_ARRAYS]
-    assert all(x.is_cuda and x.is_contiguous() for x in t)
-    check(lib().wa_beam_select_check(_dev(t[0]), *[_ptr(x) for x in t], n_clips, K, C, ctx))
-
-
-def beam_topk_rules_check(logits, kp: int, records, ts0: int, step: int = -1, suppress_eot: bool = False,
-                          eot_stop: bool = True, tok=None, lp=None, mass=None):
-    """beam_topk_check under the timestamp rules (wa_beam_topk_rules_check):
-    records int32 [R, 8], one rule record per row (timestamp_rule) -> (tokens
-    int32 [R, kp], log-probabilities f32 [R, kp], mass int32 [R]: 1 where rule f
-    fired, range flag).  A row with fewer than kp allowed ids ends in (0, -inf)
-    entries.  tok / lp / mass: output tensors to write into (flat)."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    rec = np.ascontiguousarray(records, np.int32)
-    assert rec.shape == (R, 8)
-    if tok is None:
-        tok = torch.empty((R, kp), device=logits.device, dtype=torch.int32)
-    if lp is None:
-        lp = torch.empty((R, kp), device=logits.device, dtype=torch.float32)
-    if mass is None:
-        mass = torch.empty(R, device=logits.device, dtype=torch.int32)
-    flag = ctypes.c_int32(0)
-    check(lib().wa_beam_topk_rules_check(_dev(logits), _ptr(logits), R, V, kp, 1 if suppress_eot else 0, step,
-                                         1 if eot_stop else 0, int(ts0),
-                                         rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(tok), _ptr(lp),
-                                         _ptr(mass), ctypes.byref(flag)))
-    return tok, lp, mass, int(flag.value)
-
-
-def beam_select_rules_check(arrays: dict, n_clips: int, K: int, C: int, ctx: int, ts0: int, V: int) -> None:
-    """beam_select_check with the rows' rule records, arrays["records"] cuda int32
-    [rows, 8] (None: the plain launch), advanced in place
-    (wa_beam_select_rules_check)."""
-    t = [arrays[k] for k in BEAM_SELECT_ARRAYS]
-    rec = arrays.get("records")
-    assert all(x.is_cuda and x.is_contiguous() for x in t) and (rec is None or (rec.is_cuda and rec.is_contiguous()))
-    check(lib().wa_beam_select_rules_check(_dev(t[0]), *[_ptr(x) for x in t], None if rec is None else _ptr(rec),
-                                           int(ts0), int(V), n_clips, K, C, ctx))
-
-
-def self_attention_beam_pad_check(qkv, cache_k, cache_v, anc, pad, H: int, kv_len: int,
-                                  precision: int = wq4.PREC_F16X2, f32_out: bool = False):
-    """self_attention_beam_check in the pad form of a prompted beam step
-    (wa_self_attention_beam_pad_check): pad host int32 [R], row r attends slots
-    [pad[r], kv_len] through anc."""
-    torch = _torch()
-    R, _, ctx, _ = cache_k.shape
-    assert anc.dtype == torch.int32 and anc.is_contiguous() and tuple(anc.shape) == (R, ctx)
-    pad = _i32(pad)
-    assert pad.size == R
-    out = torch.empty((R, 64 * H), device=qkv.device, dtype=torch.float32)
-    check(lib().wa_self_attention_beam_pad_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v),
-                                                 _ptr(anc), _as(pad, ctypes.c_int32), R, H, ctx, kv_len, precision,
-                                                 1 if f32_out else 0, _ptr(out)))
-    return out
-
-
 def beam_check(beam_size: int, max_candidates: int, n_clips: int, max_batch: int, null: bool = False) -> int:
     """wa_beam_check's status (0 = OK) for these arguments; null: a null wa_beam."""
     b = Beam(int(beam_size), int(max_candidates), float("nan"))
@@ -761,46 +166,6 @@ def _prompt_arrays(prompts, n: Optional[int] = None, min_len: int = 1):
     return tok, np.asarray([p.size for p in prompts], np.int32), ld
 
 
-def self_attention_pad_check(qkv, cache_k, cache_v, H: int, kv_len: int, pad, precision: int = wq4.PREC_F16X2):
-    """self_attention_check with Tq = 1 in the pad form of a prompted decode step
-    (wa_self_attention_pad_check): pad host int32 [B], clip b's entries are
-    cache slots [pad[b], kv_len)."""
-    torch = _torch()
-    B, _, ctx, _ = cache_k.shape
-    pad = _i32(pad)
-    assert pad.size == B
-    out = torch.empty((B, 64 * H), device=qkv.device, dtype=torch.float32)
-    check(lib().wa_self_attention_pad_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, H, ctx,
-                                            kv_len, _as(pad, ctypes.c_int32), precision, _ptr(out)))
-    return out
-
-
-def self_attention_prefill_check(qkv, cache_k, cache_v, P: int, pad, H: int, precision: int = wq4.PREC_F16X2):
-    """The prefill's self-attention (wa_self_attention_prefill_check): qkv cuda
-    f32 [B*P, 3*64H], pad host int32 [B] (clip b's rows are [pad[b], P)); caches
-    [B, H, ctx, 64], slots pad[b] .. P-1 written in place -> [B*P, 64H]."""
-    torch = _torch()
-    B, _, ctx, _ = cache_k.shape
-    pad = _i32(pad)
-    assert pad.size == B and qkv.shape[0] == B * P
-    out = torch.empty((B * P, 64 * H), device=qkv.device, dtype=torch.float32)
-    check(lib().wa_self_attention_prefill_check(_dev(qkv), _ptr(qkv.contiguous()), _ptr(cache_k), _ptr(cache_v), B, P,
-                                                _as(pad, ctypes.c_int32), H, ctx, precision, _ptr(out)))
-    return out
-
-
-def cross_attention_prefill_check(q, k, v, P: int, precision: int = wq4.PREC_F16X2):
-    """The prefill's cross-attention (wa_cross_attention_prefill_check): q cuda
-    f32 [B*P, 64H], k / v head-major [B, H, T, 64] -> [B*P, 64H]."""
-    torch = _torch()
-    B, H, T, _ = k.shape
-    assert q.shape == (B * P, 64 * H) and k.is_contiguous() and v.is_contiguous()
-    out = torch.empty((B * P, 64 * H), device=q.device, dtype=torch.float32)
-    check(lib().wa_cross_attention_prefill_check(_dev(q), _ptr(q.contiguous()), _ptr(k), _ptr(v), B, P, T, H,
-                                                 precision, _ptr(out)))
-    return out
-
-
 def align_words(jump, word_lens):
     """Token jump frames -> word times (wa_align_words, host only): jump the N
     frames of a clip (the last row is EOT), word_lens the words' token counts,
@@ -810,63 +175,6 @@ def align_words(jump, word_lens):
     check(lib().wa_align_words(_as(jump, ctypes.c_int32), jump.size, _as(wl, ctypes.c_int32), wl.size,
                                _as(start, ctypes.c_float), _as(end, ctypes.c_float)))
     return start, end
-
-
-def align_matrix_check(q, k, P: int, pad, heads, F, first_row: int = 0, precision: int = wq4.PREC_F16X2):
-    """The alignment's weights and filter kernels (wa_align_matrix_check): q cuda
-    f32 [B*P, 64H], k head-major [B, H, T, 64], pad / F host [B], heads the
-    layer's alignment heads -> cuda f32 [B, P, T]: row i of clip b is M of its
-    position first_row + i, zero past its N rows and F frames."""
-    torch = _torch()
-    B, H, T, _ = k.shape
-    pad, heads, F = _i32(pad), _i32(heads), _i32(F)
-    assert q.shape == (B * P, 64 * H) and k.is_contiguous() and pad.size == B and F.size == B
-    out = torch.empty((B, P, T), device=q.device, dtype=torch.float32)
-    check(lib().wa_align_matrix_check(_dev(q), _ptr(q.contiguous()), _ptr(k), B, P, _as(pad, ctypes.c_int32), T, H,
-                                      _as(heads, ctypes.c_int32), heads.size, _as(F, ctypes.c_int32), first_row,
-                                      precision, _ptr(out)))
-    return out
-
-
-def dtw_check(x, N, F, jump=None, want_trace: bool = True):
-    """The alignment's DTW kernel (wa_dtw_check): x cuda f32 [B, N_ld, F_ld]
-    costs, N / F host [B] -> (jump cuda int32 [B, N_ld], entries < N[b] written,
-    trace cuda uint8 [B, N_ld + 1, F_ld + 1] or None).  jump: a cuda int32
-    buffer of at least B * N_ld entries to write into."""
-    torch = _torch()
-    B, N_ld, F_ld = x.shape
-    N, F = _i32(N), _i32(F)
-    assert x.is_contiguous() and x.dtype == torch.float32 and N.size == B and F.size == B
-    if jump is None:
-        jump = torch.full((B, N_ld), -1, device=x.device, dtype=torch.int32)
-    assert jump.dtype == torch.int32 and jump.is_contiguous() and jump.numel() >= B * N_ld
-    trace = torch.full((B, N_ld + 1, F_ld + 1), 255, device=x.device, dtype=torch.uint8) if want_trace else None
-    check(lib().wa_dtw_check(_dev(x), _ptr(x), B, N_ld, F_ld, _as(N, ctypes.c_int32), _as(F, ctypes.c_int32),
-                             _ptr(jump), None if trace is None else _ptr(trace)))
-    return jump, trace
-
-
-def embed_pad_check(tokens, tok_emb, pos_emb, B: int, Tq: int, pos0: int, pad, use_state: bool = False, gamma=None,
-                    precision: int = wq4.PREC_F16X2):
-    """embed_check in the pad form (wa_embed_pad_check): pad host int32 [B],
-    clip b's rows get positions pos0 + t - pad[b]."""
-    torch = _torch()
-    V, D = tok_emb.shape
-    ctx = pos_emb.shape[0]
-    tokens = np.ascontiguousarray(tokens, np.int32)
-    pad = _i32(pad)
-    assert tokens.size == B * Tq and pad.size == B and tok_emb.is_contiguous() and pos_emb.is_contiguous()
-    R = B * Tq
-    x = torch.empty((R, D), device=tok_emb.device, dtype=torch.float32)
-    tiled = stats = None
-    if gamma is not None:
-        tiled = torch.zeros(wq4.lib().wq4_atiled_bytes(R, D, precision), device=tok_emb.device, dtype=torch.uint8)
-        stats = torch.empty((R, D // 16, 2), device=tok_emb.device, dtype=torch.float32)
-    check(lib().wa_embed_pad_check(_dev(tok_emb), _as(tokens, ctypes.c_int32), _ptr(tok_emb), V, _ptr(pos_emb), ctx, B,
-                                   Tq, D, pos0, 1 if use_state else 0, _as(pad, ctypes.c_int32),
-                                   None if gamma is None else _ptr(gamma), precision, _ptr(x),
-                                   None if gamma is None else _ptr(tiled), None if gamma is None else _ptr(stats)))
-    return x, tiled, stats
 
 
 def long_prompt_window(prev, reset: int, n_text_ctx: int, max_tokens: int, startofprev: int, lang_token: int,
@@ -895,51 +203,6 @@ def long_prompt_next(prev, reset: int, tokens, ts0: int, skipped: bool, temperat
     return buf[:n.value].tolist(), r.value
 
 
-def logits_argmax_check(hid, emb, step: int, precision: int = wq4.PREC_F16X2, want_logits: bool = True):
-    """The decode step's fused logits + greedy pick (wa_logits_argmax_check):
-    hid cuda f32 [B, D], emb cuda f32 [V, D] -> (tokens int32 [B], logits
-    [B, V] as the pick saw them, or None)."""
-    torch = _torch()
-    B, D = hid.shape
-    V = emb.shape[0]
-    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
-    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32) if want_logits else None
-    check(lib().wa_logits_argmax_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
-                                       precision, _ptr(tok), _ptr(lg) if lg is not None else None))
-    return tok, lg
-
-
-def logits_logprob_check(hid, emb, step: int, precision: int = wq4.PREC_F16X2, want_logits: bool = True,
-                         logprob=None):
-    """The scored form of the decode step's fused logits + greedy pick
-    (wa_logits_logprob_check): hid cuda f32 [B, D], emb cuda f32 [V, D] ->
-    (tokens int32 [B], logprob f32 = log softmax(z)[token] over the masked
-    row the pick saw, logits [B, V] or None).  logprob: an optional cuda f32
-    buffer of >= B entries to write into (entries B .. stay untouched)."""
-    torch = _torch()
-    B, D = hid.shape
-    V = emb.shape[0]
-    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
-    lp = torch.empty(B, device=hid.device, dtype=torch.float32) if logprob is None else logprob
-    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32) if want_logits else None
-    check(lib().wa_logits_logprob_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
-                                        precision, _ptr(tok), _ptr(lp), _ptr(lg) if lg is not None else None))
-    return tok, lp, lg
-
-
-def row_logprob_check(logits, lo: int, hi: int, mask_eot: bool = False, idx=None, fixed_idx: int = 0):
-    """The row kernel of the stored-logits scores (wa_row_logprob_check):
-    logits cuda f32 [R, V] -> f32 [R], z[id] - logsumexp(z[lo:hi]) per row,
-    id = idx[row] (cuda int32 [R]) or fixed_idx; EOT counts as -inf with mask_eot."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    out = torch.empty(R, device=logits.device, dtype=torch.float32)
-    check(lib().wa_row_logprob_check(_dev(logits), _ptr(logits), R, V, lo, hi, 1 if mask_eot else 0,
-                                     _ptr(idx.contiguous()) if idx is not None else None, int(fixed_idx), _ptr(out)))
-    return out
-
-
 def segments_from_tokens(tokens, ts0: int = 50365, cap: Optional[int] = None):
     """The segments of one 30-s window's tokens (wa_segments_from_tokens; host
     only): ([(start_s, end_s, tokens of the segment)], seek_frames).  ts0 is
@@ -957,72 +220,6 @@ def segments_from_tokens(tokens, ts0: int = 50365, cap: Optional[int] = None):
     return out, int(seek.value)
 
 
-def timestamp_rule(tokens, ts0: int, V: int, max_initial: int = 50) -> np.ndarray:
-    """The rule record (8 int32, RULE_FIELDS) after one clip's sampled tokens
-    (wa_timestamp_rule; host only)."""
-    toks = np.ascontiguousarray(tokens, np.int32).reshape(-1)
-    rec = np.zeros(8, np.int32)
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    check(lib().wa_timestamp_rule(toks.ctypes.data_as(i32p), int(toks.size), int(ts0), int(V), int(max_initial),
-                                  rec.ctypes.data_as(i32p)))
-    return rec
-
-
-def _records(histories, ts0: int, V: int, max_initial: int) -> np.ndarray:
-    return np.ascontiguousarray(np.stack([timestamp_rule(h, ts0, V, max_initial) for h in histories]), np.int32)
-
-
-def logits_timestamp_check(hid, emb, histories, step: int, ts0: int, max_initial: int = 50,
-                           precision: int = wq4.PREC_F16X2, logprob=None):
-    """The timestamp form of the fused logits + pick (wa_logits_timestamp_check):
-    hid cuda f32 [B, D], emb cuda f32 [V, D], histories = each row's sampled
-    tokens so far -> (tokens int32 [B], logprob f32, logits [B, V] as the pick
-    saw them: masks a-e from the kernel, rule f's mask of [0, ts0) applied
-    here where the kernel reports it, mass int32 [B])."""
-    torch = _torch()
-    B, D = hid.shape
-    V = emb.shape[0]
-    rec = _records(histories, ts0, V, max_initial)
-    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
-    mass = torch.empty(B, device=hid.device, dtype=torch.int32)
-    lp = torch.empty(B, device=hid.device, dtype=torch.float32) if logprob is None else logprob
-    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32)
-    check(lib().wa_logits_timestamp_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
-                                          precision, ts0, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                          _ptr(tok), _ptr(lp), _ptr(mass), _ptr(lg)))
-    lg[mass.bool(), :ts0] = float("-inf")
-    return tok, lp, lg, mass
-
-
-def row_timestamp_check(logits, histories, ts0: int, suppress_eot: bool = False, max_initial: int = 50):
-    """The stored-logits kernel of the timestamp rule (wa_row_timestamp_check):
-    logits cuda f32 [R, V] -> (tokens int32 [R], logprob f32 [R], mass int32 [R])."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    rec = _records(histories, ts0, V, max_initial)
-    tok = torch.empty(R, device=logits.device, dtype=torch.int32)
-    mass = torch.empty(R, device=logits.device, dtype=torch.int32)
-    lp = torch.empty(R, device=logits.device, dtype=torch.float32)
-    check(lib().wa_row_timestamp_check(_dev(logits), _ptr(logits), R, V, 1 if suppress_eot else 0, ts0,
-                                       rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), _ptr(tok), _ptr(lp),
-                                       _ptr(mass)))
-    return tok, lp, mass
-
-
-def timestamp_bookkeep_check(tokens, ts0: int, V: int, max_initial: int = 50, device: int = 0) -> np.ndarray:
-    """Token sequences int32 [R, S] through the timestamp bookkeeping kernel,
-    one token per row and launch (wa_timestamp_bookkeep_check) -> the rule
-    records after each launch, int32 [S, R, 8]."""
-    toks = np.ascontiguousarray(tokens, np.int32)
-    R, S = toks.shape
-    out = np.zeros((S, R, 8), np.int32)
-    i32p = ctypes.POINTER(ctypes.c_int32)
-    check(lib().wa_timestamp_bookkeep_check(device, toks.ctypes.data_as(i32p), R, S, int(ts0), int(V),
-                                            int(max_initial), out.ctypes.data_as(i32p)))
-    return out
-
-
 def sample_noise(seed: int, pick: int, id0: int, n: int) -> tuple[np.ndarray, np.ndarray]:
     """The sampling noise of ids id0 .. id0 + n - 1 at (seed, pick) as the
     kernels define it (wa_sample_noise; host only): (u, g) float32 [n]."""
@@ -1033,65 +230,6 @@ def sample_noise(seed: int, pick: int, id0: int, n: int) -> tuple[np.ndarray, np
     return u, g
 
 
-def _sampling_arrays(temperature, seed, n: int):
-    t = np.ascontiguousarray(np.broadcast_to(np.asarray(temperature, np.float32), (n,)))
-    s = np.ascontiguousarray(np.broadcast_to(np.asarray(seed, np.uint64), (n,)))
-    return t, s
-
-
-def logits_sample_check(hid, emb, temperature, seed, step: int, histories=None, ts0: int = 0,
-                        max_initial: int = 50, precision: int = wq4.PREC_F16X2):
-    """The sampled form of the fused logits + pick (wa_logits_sample_check) at
-    pick index step + 1: hid cuda f32 [B, D], emb cuda f32 [V, D], temperature
-    / seed per row; histories (each row's sampled tokens so far) selects the
-    timestamp form -> (tokens int32 [B], logprob f32 [B], logits [B, V] the
-    masked rows without noise -- rule f's mask applied here where the kernel
-    reports it -- and mass int32 [B], or None without histories)."""
-    torch = _torch()
-    B, D = hid.shape
-    V = emb.shape[0]
-    t, s = _sampling_arrays(temperature, seed, B)
-    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
-    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
-    mass = torch.zeros(B, device=hid.device, dtype=torch.int32) if rec is not None else None
-    lp = torch.empty(B, device=hid.device, dtype=torch.float32)
-    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32)
-    check(lib().wa_logits_sample_check(_dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step,
-                                       precision, t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                       s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(ts0),
-                                       rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None,
-                                       _ptr(tok), _ptr(lp), _ptr(mass) if mass is not None else None, _ptr(lg)))
-    if mass is not None:
-        lg[mass.bool(), :ts0] = float("-inf")
-    return tok, lp, lg, mass
-
-
-def row_sample_check(logits, temperature, seed, pick: int, suppress_eot: bool = False, histories=None, ts0: int = 0,
-                     max_initial: int = 50):
-    """The stored-logits kernel of the sampled pick (wa_row_sample_check) at
-    pick index `pick`: logits cuda f32 [R, V] -> (tokens int32 [R], logprob f32
-    [R], mass int32 [R]); histories selects the timestamp form."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    t, s = _sampling_arrays(temperature, seed, R)
-    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
-    tok = torch.empty(R, device=logits.device, dtype=torch.int32)
-    mass = torch.empty(R, device=logits.device, dtype=torch.int32)
-    lp = torch.empty(R, device=logits.device, dtype=torch.float32)
-    check(lib().wa_row_sample_check(_dev(logits), _ptr(logits), R, V, 1 if suppress_eot else 0, int(pick),
-                                    t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                                    s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), int(ts0),
-                                    rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None,
-                                    _ptr(tok), _ptr(lp), _ptr(mass)))
-    return tok, lp, mass
-
-
-def _id_list(ids):
-    a = np.ascontiguousarray(ids, np.int32).reshape(-1)
-    return a, (a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if a.size else None), int(a.size)
-
-
 def suppress_check(always=(), first=(), ts0: int = 50365) -> bool:
     """Whether the two suppress-token lists are valid for a model whose
     <|0.00|> is ts0 (wa_suppress_check; host only): `always` ids in [0, EOT) or
@@ -1099,83 +237,6 @@ def suppress_check(always=(), first=(), ts0: int = 50365) -> bool:
     _a, ap, na = _id_list(always)
     _f, fp, nf = _id_list(first)
     return lib().wa_suppress_check(ap, na, fp, nf, int(ts0)) == 0
-
-
-def logits_suppress_check(hid, emb, ids, step: int, ts0: int = 50365, temperature=None, seed=None, histories=None,
-                          max_initial: int = 50, precision: int = wq4.PREC_F16X2, scored: bool = True):
-    """The decode step's fused logits + pick under a suppress list
-    (wa_logits_suppress_check): ids = the list of that pick.  The mode as the
-    entries it extends: greedy (scored False), scored, timestamps (histories),
-    sampled (temperature / seed, histories optional) -> (tokens int32 [B],
-    logprob f32 [B] or None, logits [B, V] as the kernel's masks a-e and the
-    list left them, mass int32 [B] or None).  An empty list returns the bytes of
-    logits_argmax_check / _logprob_ / _timestamp_ / _sample_check."""
-    torch = _torch()
-    B, D = hid.shape
-    V = emb.shape[0]
-    _keep, idp, n_ids = _id_list(ids)
-    sampled = temperature is not None
-    t, s = _sampling_arrays(temperature, seed, B) if sampled else (None, None)
-    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
-    tok = torch.empty(B, device=hid.device, dtype=torch.int32)
-    want_lp = scored or sampled or rec is not None
-    lp = torch.empty(B, device=hid.device, dtype=torch.float32) if want_lp else None
-    mass = torch.zeros(B, device=hid.device, dtype=torch.int32) if rec is not None else None
-    lg = torch.empty((B, V), device=hid.device, dtype=torch.float32)
-    check(lib().wa_logits_suppress_check(
-        _dev(hid), _ptr(hid.contiguous()), _ptr(emb.contiguous()), B, D, V, step, precision, idp, n_ids,
-        t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if sampled else None,
-        s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if sampled else None, int(ts0),
-        rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None, _ptr(tok),
-        _ptr(lp) if lp is not None else None, _ptr(mass) if mass is not None else None, _ptr(lg)))
-    return tok, lp, lg, mass
-
-
-def row_suppress_check(logits, ids, ts0: int = 50365, suppress_eot: bool = False, pick: int = 0, temperature=None,
-                       seed=None, histories=None, max_initial: int = 50):
-    """The stored-logits picks under a suppress list (wa_row_suppress_check):
-    without temperature and histories the argmax and its log-probability over
-    the masked row, else the timestamp / sampled row pick -> (tokens int32 [R],
-    logprob f32 [R], mass int32 [R] or None)."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    _keep, idp, n_ids = _id_list(ids)
-    sampled = temperature is not None
-    t, s = _sampling_arrays(temperature, seed, R) if sampled else (None, None)
-    rec = _records(histories, ts0, V, max_initial) if histories is not None else None
-    tok = torch.empty(R, device=logits.device, dtype=torch.int32)
-    lp = torch.empty(R, device=logits.device, dtype=torch.float32)
-    mass = torch.zeros(R, device=logits.device, dtype=torch.int32) if (sampled or rec is not None) else None
-    check(lib().wa_row_suppress_check(
-        _dev(logits), _ptr(logits), R, V, 1 if suppress_eot else 0, int(pick), idp, n_ids,
-        t.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if sampled else None,
-        s.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if sampled else None, int(ts0),
-        rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None, _ptr(tok), _ptr(lp),
-        _ptr(mass) if mass is not None else None))
-    return tok, lp, mass
-
-
-def beam_topk_suppress_check(logits, kp: int, ids, ts0: int = 50365, records=None, step: int = -1,
-                             suppress_eot: bool = False, eot_stop: bool = True):
-    """beam_topk_check (records None) / beam_topk_rules_check under a suppress
-    list (wa_beam_topk_suppress_check) -> (tokens int32 [R, kp],
-    log-probabilities f32 [R, kp], mass int32 [R] or None, range flag)."""
-    torch = _torch()
-    logits = logits.contiguous()
-    R, V = logits.shape
-    _keep, idp, n_ids = _id_list(ids)
-    rec = np.ascontiguousarray(records, np.int32) if records is not None else None
-    assert rec is None or rec.shape == (R, 8)
-    tok = torch.empty((R, kp), device=logits.device, dtype=torch.int32)
-    lp = torch.empty((R, kp), device=logits.device, dtype=torch.float32)
-    mass = torch.empty(R, device=logits.device, dtype=torch.int32) if rec is not None else None
-    flag = ctypes.c_int32(0)
-    check(lib().wa_beam_topk_suppress_check(
-        _dev(logits), _ptr(logits), R, V, kp, 1 if suppress_eot else 0, step, 1 if eot_stop else 0, int(ts0), idp,
-        n_ids, rec.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if rec is not None else None, _ptr(tok), _ptr(lp),
-        _ptr(mass) if mass is not None else None, ctypes.byref(flag)))
-    return tok, lp, mass, int(flag.value)
 
 
 def _scored_clip(toks, n, lp, ns, lt, lpr) -> dict:
